@@ -11,11 +11,15 @@ value  : whole-job frames/s = n_gpus * B * T * steps / max-over-ranks wall time 
 
 Run:  python bench.py [--gpus N --steps K --warmup W]   (N > 1: starts N ranks itself)
       torchrun --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
-Extra objects on the JSON line: ``roofline`` (the persistent decoder attention kernel, the
-step's dominant kernel, timed live with HIP events on the stream it runs on), ``cpu_baseline``
-(the CPU oracle, bounded sample), ``median_ms_per_step`` (per-step HIP events) and, at N=1, the
-other single-GPU configs: ``c4_vctk_training`` (configs[3]) and ``c5_free_running``
-(configs[4]).  Any training step skipped by the health guard aborts the run before printing.
+A plain run sets up, warms up, times the K steps and prints the one JSON line (``ms_per_step``
+= wall time of the timed region / K, ``median_ms_per_step`` from per-step HIP events).
+``--dump-outputs DIR`` also writes what the last timed step computed as ``DIR/<name>.npy``.
+``--full`` adds the extra objects to the line: ``roofline`` / ``roofline_bptt`` (the
+persistent decoder attention kernels, the step's dominant kernels, timed live with HIP events
+on the stream they run on), ``cpu_baseline`` (the CPU oracle, bounded sample) and, at N=1, the
+other single-GPU configs: ``c4_vctk_training`` (configs[3]), ``c5_free_running`` (configs[4]),
+the ragged drop-in path and the B=64 per-step path; the ``--no-*`` switches trim ``--full``.
+Any training step skipped by the health guard aborts the run before printing.
 """
 
 from __future__ import annotations
@@ -50,6 +54,14 @@ def parse():
     ap.add_argument("--chars", type=int, default=200)
     ap.add_argument("--frames", type=int, default=1000)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the attention-kernel "
+                         "roofline probes, the CPU baselines and the other single-GPU configs "
+                         "(C4, C5, ragged drop-in, B=64 per-step path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its "
+                         "returned tensors, the updated parameters and the gradients) as "
+                         "DIR/<name>.npy (float32; a fixed seeded sample of a large array)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the C4 (VCTK training) and C5 (free-running inference) lines")
@@ -504,6 +516,29 @@ def c5_free_running(args, B=8, steps=500):
     return res
 
 
+DUMP_MAX_ELEMS = 1 << 20        # per array: 4 MiB of float32
+DUMP_MAX_BYTES = 64 << 20       # all arrays together
+
+
+def dump_outputs(path: str, arrays) -> None:
+    """--dump-outputs: one ``<name>.npy`` (float32) per array of the last timed step.  An array
+    of more than DUMP_MAX_ELEMS elements is written as a fixed sample of its flattened values
+    (indices drawn once per size from a seeded generator, sorted), so two builds run with the
+    same arguments write the same elements."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = np.atleast_1d(t.detach().to(torch.float32).cpu().numpy())
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(20240607).choice(a.size, DUMP_MAX_ELEMS,
+                                                                 replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes to write")
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -525,8 +560,9 @@ def main():
     from sat_amd import data, dp, engine, hparams, train
     hp = hparams.ljspeech_hparams()
     B, N, T = args.batch, args.chars, args.frames
-    rec = _Recorder("decoder_attention_fwd")
-    rec_bwd = _Recorder("decoder_attention_bwd")
+    roofline = args.full and not args.no_roofline
+    rec = _Recorder("decoder_attention_fwd") if roofline else None
+    rec_bwd = _Recorder("decoder_attention_bwd") if roofline else None
     model = engine.Tacotron(hp, "cuda", seed=1234, attn_tile=args.attn_tile,
                             pipeline_chunk=args.pipeline_chunk)
     dp.broadcast_params(model.params)   # identical initial weights on every replica
@@ -536,13 +572,14 @@ def main():
     trainer.batch_lengths = batch["source_length"]
     if args.no_graph:
         for _ in range(max(1, args.warmup)):
-            trainer.step(batch)
+            last = trainer.step(batch)
         run = lambda: trainer.step(batch)  # noqa: E731
     else:
         g = train.GraphedStep(trainer, batch, warmup=1)
         for _ in range(args.warmup):
             g.replay()
         run = g.replay
+        last = g.out
     torch.cuda.synchronize()
     loss0 = float(trainer.last_loss.item())
     if dist:
@@ -552,7 +589,7 @@ def main():
     t0 = time.perf_counter()
     evs[0].record()
     for i in range(args.steps):
-        run()
+        last = run()
         evs[i + 1].record()
     torch.cuda.synchronize()
     if dist:
@@ -565,10 +602,15 @@ def main():
     loss1 = float(trainer.last_loss.item())
     frames = world * B * T * args.steps
     value = frames / dt
-    roof = None if args.no_roofline else attention_probe(rec, B, N)
-    roof_bwd = None if args.no_roofline else attention_bwd_probe(rec_bwd, B, N)
+    if rank == 0 and args.dump_outputs:
+        # the step's returned tensors, then what it left behind: the parameters after its Adam
+        # update and the gradients that update consumed (before the probes of --full run)
+        dump_outputs(args.dump_outputs, {**last, "params": model.params, "grads": model.grads})
     extra = {}
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full:
+        extra["roofline"] = attention_probe(rec, B, N) if roofline else None
+        extra["roofline_bptt"] = attention_bwd_probe(rec_bwd, B, N) if roofline else None
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         extra["c4_vctk_training"] = c4_vctk_training(args)
         extra["c5_free_running"] = c5_free_running(args)
         if not args.no_ragged:
@@ -576,9 +618,11 @@ def main():
         if not args.no_fallback:
             extra["fallback_b64_per_step_path"] = fallback_training(args)
     if rank == 0:
-        cpu = None if args.no_cpu_baseline else cpu_baseline(hp, args)
-        cpu_c2 = (None if args.no_cpu_baseline or args.cpu_baseline_c2_steps <= 0
-                  else cpu_baseline(hp, args, B=B, steps=args.cpu_baseline_c2_steps))
+        if args.full:
+            cpu = not args.no_cpu_baseline
+            extra["cpu_baseline"] = cpu_baseline(hp, args) if cpu else None
+            extra["cpu_baseline_c2"] = (cpu_baseline(hp, args, B=B, steps=args.cpu_baseline_c2_steps)
+                                        if cpu and args.cpu_baseline_c2_steps > 0 else None)
         line = {
             "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
@@ -591,7 +635,7 @@ def main():
                        "decoder_steps": T // hp.outputs_per_step, "parallelism": f"dp{world}",
                        "hip_graph": not args.no_graph, "params": model.num_params},
             "median_ms_per_step": round(float(np.median(step_ms)), 3),
-            "roofline": roof, "roofline_bptt": roof_bwd, "cpu_baseline": cpu, "cpu_baseline_c2": cpu_c2, **extra,
+            **extra,
             "loss_first_timed": round(loss0, 5), "loss_last": round(loss1, 5),
         }
         print(json.dumps(line), flush=True)

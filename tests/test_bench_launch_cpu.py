@@ -21,3 +21,13 @@ def test_bench_gpus2_launches_ranks_and_prints_one_line():
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2"
     assert d["config"]["global_batch"] == 64 and d["steps"] == 2
     assert d["ms_per_step"] > 0
+
+
+def test_bench_full_and_dump_outputs_are_off_by_default(monkeypatch):
+    import bench            # the repository root is on sys.path (tests/conftest.py)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"

@@ -11,17 +11,15 @@ import _sat_path
 _sat_path.load()
 from sat_amd import data, hparams, masks, params  # noqa: E402
 
-REF = "/root/reference/examples"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_examples")
 
 
 @pytest.mark.parametrize("name,fn", [("ljspeech", hparams.ljspeech_hparams),
                                      ("vctk", hparams.vctk_hparams)])
 def test_hparams_match_reference_json(name, fn):
-    """create_hparams(json) == the preset (values read in place from the reference's example
-    config when it is present -- this container only; the GPU box has no /root/reference)."""
+    """create_hparams(json) == the preset (values read from the reference's example config,
+    stored as a fixture under tests/golden/reference_examples/)."""
     path = os.path.join(REF, name, "self-attention-tacotron.json")
-    if not os.path.exists(path):
-        pytest.skip("reference examples not present")
     hp = hparams.create_hparams(path)
     preset = fn()
     skip = {"average_mel_level_db", "stddev_mel_level_db"}  # denormalisation stats (off path)

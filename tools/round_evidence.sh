@@ -14,7 +14,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-me
   > $O/${TAG}_gputest.log 2>&1; rc=$?; tail -3 $O/${TAG}_gputest.log; stop $rc gputest
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.log 2>&1
 rc=$?; tail -2 $O/${TAG}_smoke.log; stop $rc smoke
-timeout -k 10 400 python -u bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; rc=$?
+timeout -k 10 400 python -u bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; rc=$?
 tail -c 600 $O/${TAG}_bench.json; stop $rc bench
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -o run \
   -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra \
