@@ -39,8 +39,10 @@ extern "C" {
  * (or an A/B run loading an older build through SAT_LIB_OVERRIDE) can refuse a library whose
  * structs it would misread.  5: round-5 layout (SatAttnParamGrad without zh, sat_softmax_bwd
  * with Lq / causal, SatMha.lse); 6: SatMha.wgrad_stream / wgrad_ws; 7: SatAttnParamGrad.tsplit; 8: SatMha without
- * wgrad_stream / wgrad_ws (deferred weight gradients: sat_mha_bwd_wgrad). */
-#define SAT_ABI_VERSION 8
+ * wgrad_stream / wgrad_ws (deferred weight gradients: sat_mha_bwd_wgrad); 9: the transition agent
+ * and cumulative weights of ForwardAttention (trailing fields of SatAttnStep / SatAttnStepBwd,
+ * sat_attn_agent_bwd). */
+#define SAT_ABI_VERSION 9
 
 /* ---------------------------------------------------------------- library */
 int sat_version(void);                         /* 100*major + minor */
@@ -440,7 +442,17 @@ int sat_lstm_steps_bwd(const SatLstmBwd* steps, int32_t n, void* stream);
  * Launches the tile kernel (grid ntiles x B) and the per-utterance combine kernel.
  * Outputs: s_out (softmax alignments = next location-conv input), a_out (alpha = returned
  * alignments), s2_out, contexts [c1 | c2] into ctx (row stride ctx_sb), stats [B][4] for the
- * backward.  e1/e2/part are scratch. */
+ * backward.  e1/e2/part are scratch.
+ * The two ForwardAttention options (modules/forward_attention.py:80-86, 111-121) are the trailing
+ * fields; all of them NULL (a zero-initialised struct) is the plain step above:
+ *   u_prev   [B] transition factor u_{t-1} per utterance, used instead of the scalar u;
+ *   u_out    [B] u_t = sigmoid([c1_t | q_t[:D1]] . agent_w + agent_b) (use_transition_agent;
+ *            agent_w [M1 + D1] = transition_factor_projection/kernel, agent_b [1] its bias),
+ *            formed by the combine kernel from the context it has just written: no extra launch.
+ *            A u_out request without agent_w / agent_b is refused (SAT_ERR_ARGUMENT);
+ *   state_out[B][N] = s_out + s_prev, the state the next step's location convolution reads
+ *            when cumulative_weights is on (s_out stays the plain softmax: the backward needs
+ *            both, and a difference of sums would not give it back). */
 typedef struct SatAttnStep {
   int32_t B, N, D1, M1, D2, M2, F, KW, NT, ntiles, att1_forward;
   float u;                                  /* forward-attention transition factor (0.5) */
@@ -463,6 +475,10 @@ typedef struct SatAttnStep {
                                                0 (= 16), 8, 16 or 32 */
   int32_t phases;                           /* 0 or 3: both kernels; 1: tile kernel only;
                                                2: combine only (profiling / split launches) */
+  const float* u_prev;                      /* [B] or NULL (= the scalar u) */
+  float* u_out;                             /* [B] or NULL (no transition agent) */
+  const float* agent_w; const float* agent_b; /* [M1 + D1], [1]; needed with u_out */
+  float* state_out;                         /* [B][N] or NULL (state = s_out) */
 } SatAttnStep;
 
 int sat_attn_part_stride(int32_t M1, int32_t M2);
@@ -481,7 +497,19 @@ int sat_attn_step_fwd(const SatAttnStep* args, void* stream);
  * [B][ntiles][D1+D2] per-tile query-gradient partials (overwritten), de1_out / de2_out [B][N]
  * the energy gradients of step t (history rows for sat_attn_param_grads).  Only the critical
  * path runs per step: parameter gradients are one pass after the loop (sat_attn_param_grads),
- * the value gradients dV = alignments^T dctx one batched GEMM. */
+ * the value gradients dV = alignments^T dctx one batched GEMM.
+ * Transition agent / cumulative weights (trailing fields; all zero = the plain step):
+ *   u_prev  [B] the u_{t-1} the forward step used, instead of the scalar u;
+ *   u_t     [B] the u_t step t+1 used: dalpha_t[n] = (1-u_t) Y[n] + u_t Y[n+1] is that step's
+ *           recursion (NULL: the same as u_prev, i.e. no agent);
+ *   dup     [B][ntiles] per-tile partials of du_{t-1} = sum_n Y[n] (a_prev[n-1] - a_prev[n])
+ *           (overwritten; summed in a fixed order by sat_attn_agent_bwd, no atomics);
+ *   ds_next [B][N] dL/dS_{t+1} from the step t+1 backward (NULL at the last step), ds_out [B][N]
+ *           dL/dS_t = (transposed location convolution of df_next) + ds_next, which s_t also
+ *           receives; with them s_t is the plain softmax history and s_prev the cumulative
+ *           state S_{t-1} the forward convolved;
+ *   dqp_sb  utterance stride of dqp in floats (0 = ntiles * (D1 + D2)), so that the caller can
+ *           keep one more partial row per utterance for the agent's query gradient. */
 typedef struct SatAttnStepBwd {
   int32_t B, N, D1, M1, D2, M2, F, KW, NT, ntiles, att1_forward;
   float u;
@@ -501,9 +529,31 @@ typedef struct SatAttnStepBwd {
   float* de1_out; float* de2_out;
   float* dqp;
   int32_t waves;                            /* waves per block: 0 (= 16), 4, 8 or 16 */
+  const float* u_prev; const float* u_t;
+  float* dup;
+  const float* ds_next; float* ds_out;
+  int64_t dqp_sb;
 } SatAttnStepBwd;
 
 int sat_attn_step_bwd(const SatAttnStepBwd* args, void* stream);
+
+/* Transition agent, reverse step t (one small launch BEFORE sat_attn_step_bwd of step t; u_t was
+ * read only by step t+1, whose backward wrote dup):
+ *   dz_t = (sum_tiles dup[b]) u_t (1 - u_t) -> dz_out [B] (history row for dw = sum dz [c1 | q],
+ *   db_u = sum dz after the loop); dctx[b][:M1] += dz_t agent_w[:M1]; dq_extra[b] =
+ *   [dz_t agent_w[M1:] | 0 (D2)] (overwritten), one more partial row of the step's query
+ *   gradient that reaches the query layer but not the attention bias. */
+typedef struct SatAttnAgentBwd {
+  int32_t B, ntiles, M1, D1, D2;
+  const float* dup;                         /* [B][ntiles] */
+  const float* u_t;                         /* [B] */
+  const float* agent_w;                     /* [M1 + D1] */
+  float* dz_out;                            /* [B] */
+  float* dctx; int64_t dctx_sb;             /* [B][>= M1] */
+  float* dq_extra; int64_t dq_sb;           /* [B][D1 + D2], row stride dq_sb */
+} SatAttnAgentBwd;
+
+int sat_attn_agent_bwd(const SatAttnAgentBwd* args, void* stream);
 
 /* All attention-parameter gradients of the T reverse steps in one pass over (t, b, n)
  * (ForwardAttention variables modules/forward_attention.py:16-23,68-78 and the Bahdanau

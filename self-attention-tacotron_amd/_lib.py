@@ -24,6 +24,7 @@ class SatLibraryError(RuntimeError):
         self.rc = rc
 
 
+SAT_ERR_ARGUMENT = -1
 SAT_ERR_UNSUPPORTED = -3
 
 
@@ -120,7 +121,11 @@ SatAttnStepBwd = _struct("SatAttnStepBwd", """
     f32:u ptr:dctx i64:dctx_sb ptr:ctx_t i64:ctx_sb ptr:y_next ptr:V1 ptr:V2 ptr:s_t ptr:a_t
     ptr:a_prev ptr:s_prev ptr:s2_t ptr:stats ptr:df_next ptr:q i64:q_sb ptr:K1 ptr:K2
     ptr:v1 ptr:b1 ptr:convW ptr:convb ptr:locW ptr:v2 ptr:y_out ptr:df_out ptr:de1_out ptr:de2_out
-    ptr:dqp i32:waves""")
+    ptr:dqp i32:waves ptr:u_prev ptr:u_t ptr:dup ptr:ds_next ptr:ds_out i64:dqp_sb""")
+
+SatAttnAgentBwd = _struct("SatAttnAgentBwd", """
+    i32:B i32:ntiles i32:M1 i32:D1 i32:D2 ptr:dup ptr:u_t ptr:agent_w ptr:dz_out
+    ptr:dctx i64:dctx_sb ptr:dq_extra i64:dq_sb""")
 
 SatAttnParamGrad = _struct("SatAttnParamGrad", """
     i32:T i32:B i32:N i32:D1 i32:D2 i32:F i32:KW i32:att1_forward ptr:K1 ptr:K2
@@ -183,7 +188,8 @@ SatAttnStep = _struct("SatAttnStep", """
     i32:B i32:N i32:D1 i32:M1 i32:D2 i32:M2 i32:F i32:KW i32:NT i32:ntiles i32:att1_forward
     f32:u ptr:q i64:q_sb ptr:K1 ptr:V1 ptr:K2 ptr:V2 ptr:lengths ptr:s_prev ptr:a_prev
     ptr:v1 ptr:b1 ptr:convW ptr:convb ptr:locW ptr:v2 ptr:e1 ptr:e2 ptr:part i64:part_stride
-    ptr:s_out ptr:a_out ptr:s2_out ptr:ctx i64:ctx_sb ptr:stats ptr:loc_out i32:lpp i32:phases""")
+    ptr:s_out ptr:a_out ptr:s2_out ptr:ctx i64:ctx_sb ptr:stats ptr:loc_out i32:lpp i32:phases
+    ptr:u_prev ptr:u_out ptr:agent_w ptr:agent_b ptr:state_out""")
 
 # name -> argtypes (restype is int for all but sat_last_error_string)
 SIGNATURES = {
@@ -213,6 +219,7 @@ SIGNATURES = {
     "sat_attn_step_fwd": [ctypes.POINTER(SatAttnStep), _P],
     "sat_attn_pg_stride": [_I32, _I32, _I32, _I32],
     "sat_attn_step_bwd": [ctypes.POINTER(SatAttnStepBwd), _P],
+    "sat_attn_agent_bwd": [ctypes.POINTER(SatAttnAgentBwd), _P],
     "sat_decoder_attention_fwd": [ctypes.POINTER(SatDecAttnFwd), _P],
     "sat_decoder_attention_bwd": [ctypes.POINTER(SatDecAttnBwd), _P],
     "sat_decoder_lstms_fwd": [ctypes.POINTER(SatDecLstmFwd), _P],
@@ -283,7 +290,7 @@ RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
 
 _lib: Optional[ctypes.CDLL] = None
 # include/sat_abi.h SAT_ABI_VERSION this binding's structs follow
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 def load(path: str = LIB_PATH) -> ctypes.CDLL:

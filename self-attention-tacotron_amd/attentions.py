@@ -14,6 +14,14 @@ dual-source tile kernel, with this mechanism as source 1).  Inside the decoder t
 mechanisms of ``dual_source_attention_factory`` are fused into ONE kernel per step; the
 per-mechanism call here is the plugin-level entry for stepping a single mechanism.
 
+``ForwardAttention`` takes both of the reference's constructor options
+(modules/forward_attention.py:56-57): ``use_transition_agent`` (the learned per-step transition
+factor ``u_t = sigmoid([context | processed_query] . w + b)``, :80-86, :111-114; the variables
+``transition_factor_projection/kernel`` [M + units, 1] and ``.../bias`` [1]) and
+``cumulative_weights`` (the location features are computed from the running sum of the softmax
+alignments, :118-119).  Both run inside the same two launches per step; ``BahdanauAttention``
+ignores them, as in the reference.
+
 Supported kinds on this path: ``"forward"`` (ForwardAttention), ``"additive"``
 (BahdanauAttention) and the forced-alignment kinds ``"teacher_forcing_forward"`` /
 ``"teacher_forcing_additive"`` (modules/teacher_forcing_attention.py:13-78: step ``index``
@@ -59,10 +67,6 @@ class _HipAttention:
                  query_depth: Optional[int] = None, seed: int = 1234):
         if memory.dtype != torch.float32 or not memory.is_cuda:
             raise TypeError("memory must be a float32 device tensor [B, N, M]")
-        if options.cumulative_weights:
-            raise NotImplementedError("cumulative_weights=True is not on the hot path")
-        if options.use_transition_agent:
-            raise NotImplementedError("use_transition_agent=True is not on the hot path")
         self.options = options
         self.B, self.N, self.M = memory.shape
         self.lengths = memory_sequence_length.to(device=memory.device, dtype=torch.int64)
@@ -73,7 +77,8 @@ class _HipAttention:
                 raise ValueError("query_depth is needed to create the mechanism's variables")
             specs = []
             PR._attention(specs, "m", self.kind, self.M, query_depth, self.units,
-                          int(options.attention_kernel), int(options.attention_filters))
+                          int(options.attention_kernel), int(options.attention_filters),
+                          transition_agent=bool(options.use_transition_agent))
             vals = PR.init_specs(specs, seed)
             variables = {k[2:]: torch.tensor(v, device=memory.device) for k, v in vals.items()}
         self.variables = variables
@@ -94,7 +99,7 @@ class _HipAttention:
         return torch.zeros(batch_size, self.N, dtype=dtype, device=self.values.device)
 
     # ---- one step through the tile kernel
-    def _step(self, query: torch.Tensor, s_prev, a_prev):
+    def _step(self, query: torch.Tensor, s_prev, a_prev, u_prev=None):
         B, N, dev = self.B, self.N, self.values.device
         f32 = dict(device=dev, dtype=torch.float32)
         if self._scratch is None:
@@ -112,6 +117,10 @@ class _HipAttention:
         s_out, a_out, s2 = (torch.empty(B, N, **f32) for _ in range(3))
         ctx = torch.empty(B, self.M + _DUMMY_M2, **f32)
         fwd = self.kind == "forward"
+        agent = fwd and bool(self.options.use_transition_agent)
+        cum = fwd and bool(self.options.cumulative_weights)
+        u_out = torch.empty(B, **f32) if agent else None
+        state = torch.empty(B, N, **f32) if cum else s_out
         K.attn_step_fwd(
             B=B, N=N, D1=self.units, M1=self.M, D2=_DUMMY_D2, M2=_DUMMY_M2,
             F=int(self.options.attention_filters), KW=int(self.options.attention_kernel), NT=32,
@@ -124,13 +133,18 @@ class _HipAttention:
             convb=v["location_conv/bias"] if fwd else None,
             locW=v["location_layer/kernel"] if fwd else None, v2=sc["v2"], e1=sc["e1"],
             e2=sc["e2"], part=sc["part"], part_stride=sc["pst"], s_out=s_out, a_out=a_out,
-            s2_out=s2, ctx=ctx, ctx_sb=self.M + _DUMMY_M2, stats=None)
-        return s_out, a_out, ctx[:, :self.M]
+            s2_out=s2, ctx=ctx, ctx_sb=self.M + _DUMMY_M2, stats=None,
+            u_prev=u_prev if agent or cum else None, u_out=u_out,
+            agent_w=v["transition_factor_projection/kernel"] if agent else None,
+            agent_b=v["transition_factor_projection/bias"] if agent else None,
+            state_out=state if cum else None)
+        return state, a_out, ctx[:, :self.M], u_out
 
 
 class ForwardAttention(_HipAttention):
-    """modules/forward_attention.py:48-136 (ForwardAttention, no transition agent, no
-    cumulative weights).  state = (s_{t-1}, alpha_{t-1}, u)."""
+    """modules/forward_attention.py:48-136.  state = (S_{t-1}, alpha_{t-1}, u_{t-1}): S is the
+    softmax alignments of the previous step, or their running sum with ``cumulative_weights``;
+    u [B, 1] stays 0.5 unless ``use_transition_agent`` computes a new one every step."""
 
     kind = "forward"
 
@@ -144,8 +158,9 @@ class ForwardAttention(_HipAttention):
 
     def __call__(self, query, state):                                   # :88-122
         s_prev, a_prev, u = state
-        s, a, _ = self._step(query, s_prev.contiguous(), a_prev.contiguous())
-        return a, (s, a, u)
+        u_prev = u.to(torch.float32).reshape(-1).contiguous()
+        s, a, _, u_new = self._step(query, s_prev.contiguous(), a_prev.contiguous(), u_prev)
+        return a, (s, a, u if u_new is None else u_new.view(-1, 1))
 
 
 class BahdanauAttention(_HipAttention):
@@ -158,7 +173,7 @@ class BahdanauAttention(_HipAttention):
         return self.initial_alignments(batch_size, dtype)
 
     def __call__(self, query, state):
-        s, _, _ = self._step(query, None, None)
+        s, _, _, _ = self._step(query, None, None)
         return s, s
 
 

@@ -269,8 +269,20 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
     DE2 = torch.empty(Tp, B, N, **f32)
     # per-step query gradients: per-tile partials (launch path, 8 x 32 persistent kernel) or
     # fully reduced (one part: the one-utterance-per-8-workgroups BPTT)
+    # ForwardAttention options (per-step path only): the transition agent's query gradient
+    # dz_t w[M1:] is one more partial row per utterance (it reaches the query layer through the
+    # attention RNN's reverse step and the weight GEMM below, but not the attention bias)
+    agent, cum = bool(fwd and d.transition_agent), bool(fwd and d.cumulative_weights)
+    U1, SM1 = S.get("U1"), S.get("SM1")
     dq_parts = (int(_lib.load().sat_decoder_attention_bwd_dq_parts(B, N))
-                if S.get("attn_scratch") is not None else ntiles)
+                if S.get("attn_scratch") is not None else ntiles + (1 if agent else 0))
+    tf_ = f"{a1}/transition_factor_projection"
+    if agent:
+        # DUP: per-tile partials of du_t left by step t+1's backward (zero before the last step,
+        # whose u is read by nobody); DZ [T', B]: dz_t history for dw / db_u after the loop
+        DUP, DZ = K.zeros_group((B, ntiles), (Tp, B), device=dev)
+    if cum:
+        DSC = list(K.zeros_group((B, N), (B, N), device=dev))   # dL/dS ping-pong
     DQP = torch.empty(Tp, B, dq_parts, D1 + D2, **f32)
     hc = [hc0, hc1]
     cc = [cc0, cc1]
@@ -283,12 +295,26 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
         last = t == Tp - 1
         if not last:   # [c_t | h_t] through the attention RNN's input at step t+1
             K.rowdot(DG0[t + 1], W0r, RD[t], beta=1.0)
+        ext = {}
+        if agent:
+            # dz_t into dctx_t and the extra query-gradient row, before step t's backward reads
+            # them (one small launch per reverse step, not folded into the tile kernel: every
+            # tile of the utterance would need the finished sum of the previous launch's partials
+            # AND the updated dctx row must reach the value-gradient GEMM after the loop)
+            K.attn_agent_bwd(B=B, ntiles=ntiles, M1=M1, D1=D1, D2=D2, dup=DUP, u_t=U1[t + 1],
+                             agent_w=P[f"{tf_}/kernel"], dz_out=DZ[t], dctx=RD[t], dctx_sb=R0,
+                             dq_extra=DQP[t][:, ntiles], dq_sb=dq_parts * (D1 + D2))
+            ext.update(dup=DUP)
+        if agent or cum:
+            ext.update(u_prev=U1[t], u_t=U1[t + 1], dqp_sb=dq_parts * (D1 + D2))
+        if cum:
+            ext.update(ds_next=None if last else DSC[cur], ds_out=DSC[1 - cur])
         K.attn_step_bwd(
             B=B, N=N, D1=D1, M1=M1, D2=D2, M2=M2, F=d.loc_f, KW=d.loc_k, NT=attn_tile,
             ntiles=ntiles, att1_forward=1 if fwd else 0, u=0.5, dctx=RD[t],
             dctx_sb=R0, ctx_t=S["REC0"][t + 1], ctx_sb=R0,
             y_next=None if last else YA[cur], V1=S["V1"], V2=S["V2"],
-            s_t=S["S1"][t + 1], a_t=S["AL1"][t + 1],
+            s_t=SM1[t] if cum else S["S1"][t + 1], a_t=S["AL1"][t + 1],
             a_prev=S["AL1"][t], s_prev=S["S1"][t], s2_t=S["S2"][t], stats=S["ST"][t],
             df_next=None if last or not fwd else DFH[t + 1], q=S["Q"][t], q_sb=D1 + D2,
             K1=S["K1"], K2=S["K2"],
@@ -298,7 +324,7 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
             convb=P[f"{a1}/location_conv/bias"] if fwd else None,
             locW=P[f"{a1}/location_layer/kernel"] if fwd else None,
             v2=P[f"{a2}/attention_v"], y_out=YA[1 - cur], df_out=DFH[t],
-            de1_out=DE1[t], de2_out=DE2[t], dqp=DQP[t])
+            de1_out=DE1[t], de2_out=DE2[t], dqp=DQP[t], **ext)
 
     def lstm0_desc(t, cur):
         """Reverse step t of the attention RNN: recurrent + query gradients in one dot."""
@@ -312,7 +338,7 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
                     dh_carry_out=hc[1 - cur], dc_carry_out=cc[1 - cur],
                     dq0=DQP[t][:, :, :D1], wq0=P[f"{a1}/query_layer/kernel"],
                     dq1=DQP[t][:, :, D1:], wq1=P[f"{a2}/query_layer/kernel"],
-                    dq_parts=ntiles, dq_pstride=D1 + D2, dq_bstride=ntiles * (D1 + D2))
+                    dq_parts=dq_parts, dq_pstride=D1 + D2, dq_bstride=dq_parts * (D1 + D2))
 
     def attention_step(t):
         """attention part of step t; returns the attention RNN's reverse step t (not launched)."""
@@ -397,7 +423,7 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
     def fork_wgrad():
         if aux is not None:
             aux.s.wait_stream(torch.cuda.current_stream())
-            aux.keep.extend([DG0, DG1, DG2, DQP, S])
+            aux.keep.extend([DG0, DG1, DG2, DQP, S] + ([DZ] if agent else []))
         with torch.cuda.stream(aux_s):
             dec_wgrad()
 
@@ -449,9 +475,19 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
         H0f = S["H0RAW"].view(Tp * B, A)
         DQt = DQP.view(Tp * B, dq_parts, D1 + D2)
         for tile in range(dq_parts):
+            if agent and tile == ntiles:      # the agent's row: query layer 1 only, no bias
+                K.gemm(H0f.t(), DQt[:, tile, :D1], G[f"{a1}/query_layer/kernel"], beta=1.0)
+                continue
             K.gemm(H0f.t(), DQt[:, tile, :D1], G[f"{a1}/query_layer/kernel"], beta=1.0,
                    colsum=G[f"{a1}/attention_bias"] if fwd else None)
             K.gemm(H0f.t(), DQt[:, tile, D1:], G[f"{a2}/query_layer/kernel"], beta=1.0)
+        if agent:
+            # dw = sum_{t,b} dz [c1 | pq], db_u = sum dz (the colsum row of the second product)
+            DZf = DZ.view(Tp * B, 1)
+            dwk = G[f"{tf_}/kernel"]
+            K.gemm(S["REC0"][1:].reshape(Tp * B, R0)[:, :M1].t(), DZf, dwk[:M1], beta=1.0)
+            K.gemm(S["Q"].view(Tp * B, D1 + D2)[:, :D1].t(), DZf, dwk[M1:], beta=1.0,
+                   colsum=G[f"{tf_}/bias"])
 
     if not late:
         fork_wgrad()

@@ -6,6 +6,9 @@
 //       e[n] = sum_d v[d] tanh(K1[n,d] + q[d] + l[n,d] + b[d]),  s = softmax_masked(e)
 //       a~[n] = ((1-u) a_{t-1}[n] + u a_{t-1}[n-1] + 1e-7) s[n],  a = a~ / sum(a~),  c1 = a @ V1
 //   source 2, BahdanauAttention(32): e2[n] = sum_d v2[d] tanh(K2[n,d] + q2[d]), s2 = softmax, c2 = s2 @ V2
+//   optional (forward_attention.py:111-121; separate instantiations, the default ones are unchanged):
+//       transition agent   u_t = sigmoid([c1_t | q_t[:D1]] . w + b_u), per utterance (u_prev / u_out)
+//       cumulative weights the state the next step convolves is S_t = s_t + S_{t-1} (state_out)
 //
 // Split over (utterance, tile of NT memory positions) workgroups so the step streams K1/V1/K2/V2
 // from all CUs (~14 MB per step at B=32, N=200).  Softmax normalisers factor out of the contexts,
@@ -32,6 +35,7 @@ struct AttnFwdP {
   const float* locW;                     // [F][D1]
   const float* v2;                       // [D2]
   float u;
+  const float* u_prev;                   // [B] per-utterance u (UB instantiations), else the scalar
   float* e1; float* e2;                  // [B][N]
   float* part; int64_t part_stride;      // [B][ntiles][part_stride]
   float* loc_out;                        // [B][N][F] location features (history for the bwd), nullable
@@ -48,14 +52,25 @@ struct AttnCombineP {
   float* s_out; float* a_out; float* s2_out;   // [B][N]
   float* ctx; int64_t ctx_sb;                  // [B][M1 + M2] (row stride ctx_sb)
   float* stats;                                // [B][4]: M1, Z1, A1/Z1 (= sum g s), Z2 for the bwd
+  // transition agent / cumulative weights (EXT instantiation only)
+  int D1;
+  const float* u_prev; float* u_out;           // [B]
+  const float* agent_w; const float* agent_b;  // [M1 + D1], [1]
+  const float* q; int64_t q_sb;                // processed queries (the agent reads q[:D1])
+  const float* s_prev; float* state_out;       // [B][N]: state_out = s + s_prev
 };
 
 // Per-utterance combine: all loads issued at entry, tile headers reduced by one wave.
 // (A last-tile-block fusion into the tile kernel was measured slower: the device-scope fence it
 // needs writes back the XCD's L2, 12 -> 29 us per step.)
+// EXT: per-utterance u_prev, the transition agent's u_out (from the c1 this block has just
+// formed: no extra launch) and the cumulative state; EXT = false is the code as it always was.
+template <bool EXT>
 __device__ __forceinline__ void combine_utterance(const AttnCombineP& p, int b) {
   __shared__ float sc1[64], sc2[64];
   __shared__ float hdr[6];
+  __shared__ float zred[4];
+  const float u = (EXT && p.u_prev) ? p.u_prev[b] : p.u;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t rb = (int64_t)b * p.N;
   const float* part = p.part + (int64_t)b * p.ntiles * p.part_stride;
@@ -103,6 +118,7 @@ __device__ __forceinline__ void combine_utterance(const AttnCombineP& p, int b) 
   const float inv1 = 1.f / (p.att1_forward ? A1 : Z1);
   const float invz1 = 1.f / Z1, invz2 = 1.f / Z2;
   float* ctx = p.ctx + (int64_t)b * p.ctx_sb;
+  float zacc = 0.f;   // EXT: this thread's share of [c1 | q] . w
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int d = tid + 256 * h;
@@ -112,7 +128,19 @@ __device__ __forceinline__ void combine_utterance(const AttnCombineP& p, int b) 
 #pragma unroll
       for (int j = 0; j < 16; ++j)
         if (j < p.ntiles) acc = fmaf(cpart[h][j], first ? sc1[j] : sc2[j], acc);
-      ctx[d] = acc * (first ? inv1 : invz2);
+      const float cv = acc * (first ? inv1 : invz2);
+      ctx[d] = cv;
+      if (EXT && p.u_out && first) zacc = fmaf(cv, p.agent_w[d], zacc);
+    }
+  }
+  if (EXT && p.u_out) {   // u_t = sigmoid([c1_t | pq_t] . w + b_u)   (forward_attention.py:112-114)
+    if (tid < p.D1) zacc = fmaf(p.q[(int64_t)b * p.q_sb + tid], p.agent_w[p.M1 + tid], zacc);
+    zacc = wave_sum(zacc);
+    if (lane == 0) zred[wave] = zacc;
+    __syncthreads();
+    if (tid == 0) {
+      const float z = (zred[0] + zred[1]) + (zred[2] + zred[3]) + p.agent_b[0];
+      p.u_out[b] = 1.f / (1.f + expf(-z));
     }
   }
 #pragma unroll
@@ -124,12 +152,14 @@ __device__ __forceinline__ void combine_utterance(const AttnCombineP& p, int b) 
     const float s = pe * invz1;
     p.s_out[rb + n] = s;
     p.s2_out[rb + n] = pe2 * invz2;
-    p.a_out[rb + n] = p.att1_forward ? ((1.f - p.u) * apv[i] + p.u * amv[i] + 1e-7f) * pe * inv1 : s;
+    p.a_out[rb + n] = p.att1_forward ? ((1.f - u) * apv[i] + u * amv[i] + 1e-7f) * pe * inv1 : s;
+    if (EXT && p.state_out) p.state_out[rb + n] = s + p.s_prev[rb + n];
   }
 }
 
+template <bool EXT>
 __global__ void __launch_bounds__(256) attn_combine_kernel(AttnCombineP p) {
-  combine_utterance(p, blockIdx.x);
+  combine_utterance<EXT>(p, blockIdx.x);
 }
 
 // Tile kernel (NT = 32 memory positions per workgroup, 256 threads = 32 positions x 8 lanes).
@@ -142,7 +172,8 @@ __global__ void __launch_bounds__(256) attn_combine_kernel(AttnCombineP p) {
 // Block -> (b, tile): b = blockIdx % B keeps all tiles of an utterance on one XCD.
 constexpr int kNT = 32;
 
-template <int F, int DW4, int D2W4, bool FWD>
+// UB: the forward recursion's u is per utterance (p.u_prev[b]) instead of the scalar p.u.
+template <int F, int DW4, int D2W4, bool FWD, bool UB = false>
 __global__ void __launch_bounds__(256) attn_energy_kernel(AttnFwdP p) {
   constexpr int NT = kNT;
   constexpr int LD = DW4 * 32;                    // padded energy width
@@ -287,7 +318,8 @@ __global__ void __launch_bounds__(256) attn_energy_kernel(AttnFwdP p) {
     const float pe = (e1v == -INFINITY) ? 0.f : expf(e1v - m1);
     const float pe2 = (e2v == -INFINITY) ? 0.f : expf(e2v - m2);
     float w = pe;
-    if (FWD && lane < nt) w = ((1.f - p.u) * ap[lane + 1] + p.u * ap[lane] + 1e-7f) * pe;
+    const float u = UB ? p.u_prev[b] : p.u;
+    if (FWD && lane < nt) w = ((1.f - u) * ap[lane + 1] + u * ap[lane] + 1e-7f) * pe;
     if (lane < NT) { w1s[lane] = lane < nt ? w : 0.f; w2s[lane] = lane < nt ? pe2 : 0.f; }
     const float z1 = wave_sum_dpp(pe), a1 = wave_sum_dpp(lane < nt ? w : 0.f),
                 z2 = wave_sum_dpp(pe2);
@@ -335,7 +367,7 @@ __global__ void __launch_bounds__(256) attn_energy_kernel(AttnFwdP p) {
 // 1024), so each lane's serial chain is 64 / LPP float4 of the (zero padded to 256) energy row;
 // the step is latency-bound, and more, shorter chains per block hide the exp / rcp / LDS
 // latencies.  Source 2 (D2 <= 4 * LPP) takes one float4 per lane.  Same partial record.
-template <int F, int LPP, bool FWD>
+template <int F, int LPP, bool FWD, bool UB = false>
 __global__ void __launch_bounds__(kNT * LPP) attn_energy_wide_kernel(AttnFwdP p) {
   constexpr int NT = kNT, NTH = NT * LPP, NW = NTH / 64;
   constexpr int J = 64 / LPP;                      // float4 of the padded energy row per lane
@@ -475,7 +507,8 @@ __global__ void __launch_bounds__(kNT * LPP) attn_energy_wide_kernel(AttnFwdP p)
     const float pe = (e1v == -INFINITY) ? 0.f : expf(e1v - m1);
     const float pe2 = (e2v == -INFINITY) ? 0.f : expf(e2v - m2);
     float w = pe;
-    if (FWD && lane < nt) w = ((1.f - p.u) * ap[lane + 1] + p.u * ap[lane] + 1e-7f) * pe;
+    const float u = UB ? p.u_prev[b] : p.u;
+    if (FWD && lane < nt) w = ((1.f - u) * ap[lane + 1] + u * ap[lane] + 1e-7f) * pe;
     if (lane < NT) { w1s[lane] = lane < nt ? w : 0.f; w2s[lane] = lane < nt ? pe2 : 0.f; }
     const float z1 = wave_sum_dpp(pe), a1 = wave_sum_dpp(lane < nt ? w : 0.f),
                 z2 = wave_sum_dpp(pe2);
@@ -593,7 +626,14 @@ extern "C" int sat_attn_step_fwd(const SatAttnStep* a, void* stream) {
                 "sat_attn_step_fwd: null pointer");
   SAT_CHECK_ARG(!a->att1_forward || (a->s_prev && a->a_prev && a->convW && a->convb && a->locW),
                 "sat_attn_step_fwd: forward attention needs state and location weights");
+  // transition agent / cumulative weights: all-NULL (a zero-initialised struct) is today's path
+  const bool ext = a->u_prev || a->u_out || a->state_out;
+  SAT_CHECK_ARG(!ext || (a->att1_forward && a->F > 0),
+                "sat_attn_step_fwd: u_prev / u_out / state_out need forward attention");
+  SAT_CHECK_ARG(!a->u_out || (a->agent_w && a->agent_b),
+                "sat_attn_step_fwd: u_out (transition agent) needs agent_w and agent_b");
   AttnFwdP p;
+  p.u_prev = a->u_prev;
   p.B = a->B; p.N = a->N; p.D1 = a->D1; p.M1 = a->M1; p.D2 = a->D2; p.M2 = a->M2;
   p.F = a->F; p.KW = a->KW; p.NT = a->NT; p.ntiles = a->ntiles; p.att1_forward = a->att1_forward;
   p.q = a->q; p.q_sb = a->q_sb; p.K1 = a->K1; p.V1 = a->V1; p.K2 = a->K2; p.V2 = a->V2;
@@ -608,7 +648,18 @@ extern "C" int sat_attn_step_fwd(const SatAttnStep* a, void* stream) {
     const dim3 grid(a->ntiles * a->B);
     const int lpp = a->lpp == 0 ? 16 : a->lpp;
     SAT_CHECK_ARG(lpp == 8 || lpp == 16 || lpp == 32, "sat_attn_step_fwd: lpp in {8, 16, 32}");
-    if (lpp == 16 && a->att1_forward && a->F == 5)
+    if (a->u_prev) {   // per-utterance u: the same kernels, UB instantiations
+      if (lpp == 16 && a->F == 5)
+        hipLaunchKernelGGL((attn_energy_wide_kernel<5, 16, true, true>), grid, dim3(kNT * 16), 0, s, p);
+      else if (lpp == 32 && a->F == 5)
+        hipLaunchKernelGGL((attn_energy_wide_kernel<5, 32, true, true>), grid, dim3(kNT * 32), 0, s, p);
+      else if (lpp != 8)
+        hipLaunchKernelGGL((attn_energy_wide_kernel<8, 16, true, true>), grid, dim3(kNT * 16), 0, s, p);
+      else if (a->F == 5 && a->D1 == 224 && a->D2 == 32)
+        hipLaunchKernelGGL((attn_energy_kernel<5, 7, 1, true, true>), grid, dim3(256), 0, s, p);
+      else
+        hipLaunchKernelGGL((attn_energy_kernel<8, 8, 2, true, true>), grid, dim3(256), 0, s, p);
+    } else if (lpp == 16 && a->att1_forward && a->F == 5)
       hipLaunchKernelGGL((attn_energy_wide_kernel<5, 16, true>), grid, dim3(kNT * 16), 0, s, p);
     else if (lpp == 32 && a->att1_forward && a->F == 5)
       hipLaunchKernelGGL((attn_energy_wide_kernel<5, 32, true>), grid, dim3(kNT * 32), 0, s, p);
@@ -631,7 +682,11 @@ extern "C" int sat_attn_step_fwd(const SatAttnStep* a, void* stream) {
   c.e1 = a->e1; c.e2 = a->e2; c.part = a->part; c.part_stride = a->part_stride;
   c.a_prev = a->a_prev; c.s_out = a->s_out; c.a_out = a->a_out; c.s2_out = a->s2_out;
   c.ctx = a->ctx; c.ctx_sb = a->ctx_sb; c.stats = a->stats;
-  hipLaunchKernelGGL(attn_combine_kernel, dim3(a->B), dim3(256), 0, s, c);
+  c.D1 = a->D1; c.u_prev = a->u_prev; c.u_out = a->u_out; c.agent_w = a->agent_w;
+  c.agent_b = a->agent_b; c.q = a->q; c.q_sb = a->q_sb; c.s_prev = a->s_prev;
+  c.state_out = a->state_out;
+  if (ext) hipLaunchKernelGGL(attn_combine_kernel<true>, dim3(a->B), dim3(256), 0, s, c);
+  else hipLaunchKernelGGL(attn_combine_kernel<false>, dim3(a->B), dim3(256), 0, s, c);
   SAT_LAUNCH_CHECK("sat_attn_step_fwd(combine)");
   return SAT_OK;
 }
@@ -678,6 +733,12 @@ struct AttnBwdP {
   float* df_out;
   float* de1_out; float* de2_out;
   float* dqp;
+  // transition agent / cumulative weights (EXT instantiations only)
+  const float* u_prev;                 // [B] u_{t-1} per utterance (NULL: the scalar u)
+  const float* u_t;                    // [B] u_t, the factor step t+1 used (NULL: as u_prev)
+  float* dup;                          // [B][ntiles] per-tile partials of du_{t-1} (nullable)
+  const float* ds_next; float* ds_out; // [B][N] dL/dS_t in, dL/dS_{t-1}'s pass-through part out
+  int64_t dqp_sb;                      // utterance stride of dqp (room for the agent's extra part)
 };
 
 // LDS: df_next of the whole utterance early, the per-wave dq partials late
@@ -686,7 +747,12 @@ static_assert(kBwdScratch >= 16 * (kMaxD + 64), "dq flush must fit the scratch")
 
 // WAVES waves per block (NT / WAVES tile positions per wave): the step is latency-bound, so
 // more, shorter per-wave chains (8 waves = 2 per SIMD) hide the LDS / transcendental latencies.
-template <int NT, int F, int WAVES>
+// EXT (separate instantiations; EXT = false is the code as it always was): per-utterance u,
+// the per-tile partials of du_{t-1} = sum_n Y[n] (alpha_{t-1}[n-1] - alpha_{t-1}[n]) (summed by
+// sat_attn_agent_bwd: no atomics), and the cumulative state's gradient: with S_t = s_t + S_{t-1}
+// the gradient reaching S_t is DSN[n] + dS_{t+1}[n] (ds_next), which is both what s_t receives
+// and what is handed on to step t-1 (ds_out).
+template <int NT, int F, int WAVES, bool EXT = false>
 __global__ void __launch_bounds__(64 * WAVES) attn_bwd_kernel(AttnBwdP p) {
   constexpr int NTH = 64 * WAVES;
   constexpr int PPW = NT / WAVES;
@@ -704,13 +770,16 @@ __global__ void __launch_bounds__(64 * WAVES) attn_bwd_kernel(AttnBwdP p) {
   __shared__ float de1[NT], de2[NT];
   __shared__ float red[3 * WAVES];
   __shared__ float scratch[kBwdScratch];
+  __shared__ float yv[EXT ? NT : 1];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x % p.B, tile = blockIdx.x / p.B;
   const int n0 = tile * NT, nt = min(NT, p.N - n0);
   const int64_t rb = (int64_t)b * p.N;
   const int padl = (p.KW - 1) / 2;
-  const float u = p.u;
+  const float u = (EXT && p.u_prev) ? p.u_prev[b] : p.u;
+  // dalpha_t = (1 - u_t) Y_{t+1}[n] + u_t Y_{t+1}[n+1] is step t+1's recursion: its factor
+  const float un = (EXT && p.u_t) ? p.u_t[b] : u;
   const int D1 = p.D1, D2 = p.D2, N = p.N, M1 = p.M1, M2 = p.M2;
   const bool has_next = p.y_next != nullptr;     // false at the last decoder step
 
@@ -792,7 +861,7 @@ __global__ void __launch_bounds__(64 * WAVES) attn_bwd_kernel(AttnBwdP p) {
   for (int i = 0; i < kPos; ++i) {
     const int n = tid + NTH * i;
     if (n >= N) break;
-    const float dan = (1.f - u) * ry0[i] + u * ry1[i];
+    const float dan = EXT ? (1.f - un) * ry0[i] + un * ry1[i] : (1.f - u) * ry0[i] + u * ry1[i];
     s1 = fmaf(dan, rat[i], s1);
     float dsn = 0.f;
     if (FWD && has_next) {
@@ -802,10 +871,17 @@ __global__ void __launch_bounds__(64 * WAVES) attn_bwd_kernel(AttnBwdP p) {
 #pragma unroll
         for (int f = 0; f < F; ++f) dsn = fmaf(dfall[m * F + f], cw[j * F + f], dsn);
       }
+      if (!EXT) s2 = fmaf(rst[i], dsn, s2);
+    }
+    if (EXT) {
+      if (p.ds_next) dsn += p.ds_next[rb + n];
       s2 = fmaf(rst[i], dsn, s2);
     }
     const int r = n - n0;
-    if (r >= 0 && r < nt) { dsn_t[r] = dsn; dan_t[r] = dan; }
+    if (r >= 0 && r < nt) {
+      dsn_t[r] = dsn; dan_t[r] = dan;
+      if (EXT && p.ds_out) p.ds_out[rb + n] = dsn;
+    }
   }
   if (FWD) {  // location features of the tile
     if (tid < NT * F) {
@@ -853,6 +929,7 @@ __global__ void __launch_bounds__(64 * WAVES) attn_bwd_kernel(AttnBwdP p) {
         const float prior = (1.f - u) * apv[nl + 1] + u * apv[nl] + 1e-7f;
         ds = dsn_t[nl] + da * prior;
         p.y_out[rb + n] = st * da;
+        if (EXT) yv[nl] = st * da;
       } else {
         ds = DA;
       }
@@ -864,6 +941,11 @@ __global__ void __launch_bounds__(64 * WAVES) attn_bwd_kernel(AttnBwdP p) {
     }
   }
   __syncthreads();
+  if (EXT && p.dup && wave == 0) {   // this tile's share of du_{t-1} (apv[i] = alpha_{t-1}[n0-1+i])
+    const float v = lane < nt ? yv[lane] * (apv[lane] - apv[lane + 1]) : 0.f;
+    const float du = wave_sum(v);
+    if (lane == 0) p.dup[b * p.ntiles + tile] = du;
+  }
 
   // ---------------- recompute the tile's energies, back-propagate through tanh: the query
   //                  gradient and the location-feature gradient (the critical path); the
@@ -914,7 +996,8 @@ __global__ void __launch_bounds__(64 * WAVES) attn_bwd_kernel(AttnBwdP p) {
     const int nl = tid / F, f = tid - nl * F;
     p.df_out[(rb + n0 + nl) * F + f] = dfs[nl][f];
   }
-  float* dqp = p.dqp + ((int64_t)b * p.ntiles + tile) * (D1 + D2);
+  float* dqp = EXT ? p.dqp + (int64_t)b * p.dqp_sb + (int64_t)tile * (D1 + D2)
+                   : p.dqp + ((int64_t)b * p.ntiles + tile) * (D1 + D2);
   for (int d = tid; d < D1 + D2; d += NTH) {
     const int o = d < D1 ? d : kMaxD + (d - D1);
     float acc = 0.f;
@@ -1155,8 +1238,21 @@ __global__ void __launch_bounds__(256) attn_param_grad_kernel(SatAttnParamGrad p
 }
 
 template <int NT, int WAVES>
-void launch_attn_bwd(const AttnBwdP& p, int F, int blocks, hipStream_t s) {
+void launch_attn_bwd(const AttnBwdP& p, int F, int blocks, hipStream_t s, bool ext) {
   const dim3 g(blocks), blk(64 * WAVES);
+  if (ext) {   // F in 1..8 (checked by the entry point)
+    switch (F) {
+      case 1: hipLaunchKernelGGL((attn_bwd_kernel<NT, 1, WAVES, true>), g, blk, 0, s, p); break;
+      case 2: hipLaunchKernelGGL((attn_bwd_kernel<NT, 2, WAVES, true>), g, blk, 0, s, p); break;
+      case 3: hipLaunchKernelGGL((attn_bwd_kernel<NT, 3, WAVES, true>), g, blk, 0, s, p); break;
+      case 4: hipLaunchKernelGGL((attn_bwd_kernel<NT, 4, WAVES, true>), g, blk, 0, s, p); break;
+      case 5: hipLaunchKernelGGL((attn_bwd_kernel<NT, 5, WAVES, true>), g, blk, 0, s, p); break;
+      case 6: hipLaunchKernelGGL((attn_bwd_kernel<NT, 6, WAVES, true>), g, blk, 0, s, p); break;
+      case 7: hipLaunchKernelGGL((attn_bwd_kernel<NT, 7, WAVES, true>), g, blk, 0, s, p); break;
+      default: hipLaunchKernelGGL((attn_bwd_kernel<NT, 8, WAVES, true>), g, blk, 0, s, p); break;
+    }
+    return;
+  }
   switch (F) {
     case 0: hipLaunchKernelGGL((attn_bwd_kernel<NT, 0, WAVES>), g, blk, 0, s, p); break;
     case 1: hipLaunchKernelGGL((attn_bwd_kernel<NT, 1, WAVES>), g, blk, 0, s, p); break;
@@ -1272,6 +1368,15 @@ extern "C" int sat_attn_step_bwd(const SatAttnStepBwd* a, void* stream) {
   p.K1 = a->K1; p.K2 = a->K2; p.v1 = a->v1; p.b1 = a->b1; p.convW = a->convW; p.convb = a->convb;
   p.locW = a->locW; p.v2 = a->v2; p.y_out = a->y_out; p.df_out = a->df_out;
   p.de1_out = a->de1_out; p.de2_out = a->de2_out; p.dqp = a->dqp;
+  // transition agent / cumulative weights: all-zero (a zero-initialised struct) is today's path
+  const bool ext = a->u_prev || a->u_t || a->dup || a->ds_next || a->ds_out || a->dqp_sb != 0;
+  SAT_CHECK_ARG(!ext || (a->att1_forward && a->F >= 1),
+                "sat_attn_step_bwd: u_prev / dup / ds_next / ds_out need forward attention");
+  SAT_CHECK_ARG(a->dqp_sb == 0 || a->dqp_sb >= (int64_t)a->ntiles * (a->D1 + a->D2),
+                "sat_attn_step_bwd: dqp_sb below ntiles * (D1 + D2)");
+  SAT_CHECK_ARG(!a->ds_next || a->y_next, "sat_attn_step_bwd: ds_next without y_next");
+  p.u_prev = a->u_prev; p.u_t = a->u_t; p.dup = a->dup; p.ds_next = a->ds_next; p.ds_out = a->ds_out;
+  p.dqp_sb = a->dqp_sb != 0 ? a->dqp_sb : (int64_t)a->ntiles * (a->D1 + a->D2);
 
   hipStream_t s = as_stream(stream);
   const int blocks = a->B * a->ntiles;
@@ -1281,16 +1386,50 @@ extern "C" int sat_attn_step_bwd(const SatAttnStepBwd* a, void* stream) {
   const int waves = a->waves == 0 ? 16 : a->waves;
   SAT_CHECK_ARG(waves == 4 || waves == 8 || waves == 16, "sat_attn_step_bwd: waves in {4, 8, 16}");
   SAT_CHECK_ARG(a->NT >= waves || a->NT == 8, "sat_attn_step_bwd: NT >= waves");
-  if (a->NT == 8) launch_attn_bwd<8, 4>(p, F, blocks, s);
+  if (a->NT == 8) launch_attn_bwd<8, 4>(p, F, blocks, s, ext);
   else if (a->NT == 16) {
-    if (waves == 4) launch_attn_bwd<16, 4>(p, F, blocks, s);
-    else if (waves == 8) launch_attn_bwd<16, 8>(p, F, blocks, s);
-    else launch_attn_bwd<16, 16>(p, F, blocks, s);
+    if (waves == 4) launch_attn_bwd<16, 4>(p, F, blocks, s, ext);
+    else if (waves == 8) launch_attn_bwd<16, 8>(p, F, blocks, s, ext);
+    else launch_attn_bwd<16, 16>(p, F, blocks, s, ext);
   } else {
-    if (waves == 4) launch_attn_bwd<32, 4>(p, F, blocks, s);
-    else if (waves == 8) launch_attn_bwd<32, 8>(p, F, blocks, s);
-    else launch_attn_bwd<32, 16>(p, F, blocks, s);
+    if (waves == 4) launch_attn_bwd<32, 4>(p, F, blocks, s, ext);
+    else if (waves == 8) launch_attn_bwd<32, 8>(p, F, blocks, s, ext);
+    else launch_attn_bwd<32, 16>(p, F, blocks, s, ext);
   }
   SAT_LAUNCH_CHECK("sat_attn_step_bwd");
+  return SAT_OK;
+}
+
+// ---------------------------------------------------------------- transition agent, backward
+// One small launch per reverse step t, before sat_attn_step_bwd(t): u_t = sigmoid(z_t) was read
+// only by step t+1, whose backward left the per-tile partials of du_t; so
+//   dz_t = (sum_tiles dup) u_t (1 - u_t),  dctx_t[:M1] += dz_t w[:M1],  dq_extra = dz_t w[M1:]
+// (dq_extra is one more "tile" row of the query-gradient partials: it reaches the query layer
+// but not the attention bias), and dz_t is kept for dw / db_u after the loop.
+namespace sat {
+namespace {
+__global__ void __launch_bounds__(256) attn_agent_bwd_kernel(SatAttnAgentBwd p) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  float du = 0.f;
+  for (int j = 0; j < p.ntiles; ++j) du += p.dup[b * p.ntiles + j];   // fixed order
+  const float u = p.u_t[b];
+  const float dz = du * u * (1.f - u);
+  if (tid == 0) p.dz_out[b] = dz;
+  float* dc = p.dctx + (int64_t)b * p.dctx_sb;
+  for (int d = tid; d < p.M1; d += 256) dc[d] = fmaf(dz, p.agent_w[d], dc[d]);
+  float* dq = p.dq_extra + (int64_t)b * p.dq_sb;
+  for (int d = tid; d < p.D1 + p.D2; d += 256) dq[d] = d < p.D1 ? dz * p.agent_w[p.M1 + d] : 0.f;
+}
+}  // namespace
+}  // namespace sat
+
+extern "C" int sat_attn_agent_bwd(const SatAttnAgentBwd* a, void* stream) {
+  SAT_CHECK_ARG(a && a->B > 0 && a->ntiles > 0 && a->M1 > 0 && a->D1 > 0 && a->D2 >= 0,
+                "sat_attn_agent_bwd: bad sizes");
+  SAT_CHECK_ARG(a->dup && a->u_t && a->agent_w && a->dz_out && a->dctx && a->dq_extra,
+                "sat_attn_agent_bwd: null pointer");
+  SAT_CHECK_ARG(a->dctx_sb >= a->M1 && a->dq_sb >= a->D1 + a->D2, "sat_attn_agent_bwd: strides");
+  hipLaunchKernelGGL(attn_agent_bwd_kernel, dim3(a->B), dim3(256), 0, as_stream(stream), *a);
+  SAT_LAUNCH_CHECK("sat_attn_agent_bwd");
   return SAT_OK;
 }

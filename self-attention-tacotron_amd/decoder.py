@@ -108,6 +108,14 @@ def persistent_ineligible_reason(d: Dims, B: int, N: int, attn_tile: int = 32) -
     per 8 workgroups for N <= 256, four per 32 otherwise, all of them resident on 256 CUs)."""
     if not (d.att1 == "forward" and d.att2 == "additive"):
         return f"attention kinds ({d.att1}, {d.att2}) are not (forward, additive)"
+    # the persistent chain carries one scalar u and the plain softmax state (the per-step path
+    # has the per-utterance u_t and the cumulative state, DESIGN.md)
+    if d.transition_agent:
+        return ("use_forward_attention_transition_agent=True: the persistent kernels take a "
+                "scalar transition factor")
+    if d.cumulative_weights:
+        return ("cumulative_weights=True: the persistent kernels convolve the plain softmax "
+                "state")
     if attn_tile != 32:
         return f"attn_tile {attn_tile} != 32"
     dims = (d.att_rnn, d.m1, d.m2, d.d1, d.d2, d.loc_f, d.loc_k, d.dec)
@@ -246,6 +254,14 @@ def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m
     if d.att2 != "additive":
         raise NotImplementedError("attention2 must be 'additive' (hparams.py:98)")
     a1 = "decoder/attention1"
+    # ForwardAttention options (per-step path only; persistent_ineligible_reason keeps them off
+    # the persistent kernels): U1 [T'+1, B] the transition factors (row 0 = 0.5,
+    # forward_attention.py:135; without the agent every row stays 0.5), and with cumulative
+    # weights S1 holds the running sums the location conv reads while SM1 keeps the softmax
+    agent, cum = bool(att1_fwd and d.transition_agent), bool(att1_fwd and d.cumulative_weights)
+    U1 = K.fill_(torch.empty(Tp + 1, B, **f32), 0.5) if agent or cum else None
+    SM1 = torch.empty(Tp, B, N, **f32) if cum else None
+    tf_ = f"{a1}/transition_factor_projection"
     Wr0 = W0[p_w:]
     # query layers of both mechanisms, transposed once per step so the per-decoder-step query
     # product is a skinny row-dot ([B, A] x [D1+D2, A]^T)
@@ -279,8 +295,12 @@ def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m
             convb=P[f"{a1}/location_conv/bias"] if att1_fwd else None,
             locW=P[f"{a1}/location_layer/kernel"] if att1_fwd else None,
             v2=P["decoder/attention2/attention_v"], e1=E1, e2=E2, part=PART, part_stride=pst,
-            s_out=S1[t + 1], a_out=AL1[t + 1], s2_out=S2[t], ctx=REC0[t + 1], ctx_sb=R0,
-            stats=ST[t], loc_out=None if LOC is None else LOC[t])
+            s_out=SM1[t] if cum else S1[t + 1], a_out=AL1[t + 1], s2_out=S2[t],
+            ctx=REC0[t + 1], ctx_sb=R0, stats=ST[t], loc_out=None if LOC is None else LOC[t],
+            u_prev=None if U1 is None else U1[t], u_out=U1[t + 1] if agent else None,
+            agent_w=P[f"{tf_}/kernel"] if agent else None,
+            agent_b=P[f"{tf_}/bias"] if agent else None,
+            state_out=S1[t + 1] if cum else None)
 
     # ---- decoder LSTM 1: input o_t = [h0'_t | c1_t | c2_t]  (ConcatOutputAndAttentionWrapper)
     W1 = P["decoder/lstm1/kernel"]                   # [A + M1 + M2 + D, 4D]
@@ -371,7 +391,7 @@ def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m
             if i in x2_at:
                 x2_chunk(*x2_at[i])
     S.update(X0=X0, REC0=REC0, C0=C0, H0RAW=H0RAW, G0=G0, Q=Q, S1=S1, AL1=AL1, S2=S2, ST=ST,
-             LOC=LOC)
+             LOC=LOC, U1=U1, SM1=SM1)
     H1RAW, C1S, H1S, G1 = L1
     H2RAW, C2S, H2S, G2 = L2
     S.update(X1=X1, H1RAW=H1RAW, C1S=C1S, H1S=H1S, G1=G1, X2=X2, H2RAW=H2RAW, C2S=C2S,

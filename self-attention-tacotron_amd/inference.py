@@ -143,6 +143,10 @@ class FreeRunningDecoder:
         for k, v in dims.items():
             if getattr(d, k) != v:
                 return f"{k}={getattr(d, k)!r}, needs {v!r}"
+        if d.transition_agent or d.cumulative_weights:
+            # sat_decode_persistent carries a scalar u and the plain softmax state
+            return ("use_forward_attention_transition_agent / cumulative_weights are on the "
+                    "per-step path only")
         if hp.n_feed_frame != 1:
             return "n_feed_frame != 1"
         if self.forced is not None or self.feed != "mel":
@@ -297,6 +301,13 @@ class FreeRunningDecoder:
         pl.S1 = S1 = torch.zeros(Tm + 1, B, N, **f32)
         pl.AL1 = AL1 = torch.zeros(Tm + 1, B, N, **f32)
         pl.S2 = S2 = torch.zeros(Tm, B, N, **f32)
+        # ForwardAttention options: per-utterance transition factors (row 0 = 0.5; refilled per
+        # run) and, with cumulative weights, S1 as the running sum beside a scratch softmax row
+        agent = bool(att1_fwd and d.transition_agent)
+        cum = bool(att1_fwd and d.cumulative_weights)
+        pl.U1 = U1 = torch.empty(Tm + 1, B, **f32) if agent or cum else None
+        SMX1 = torch.empty(B, N, **f32) if cum else None
+        tf_ = f"{a1}/transition_factor_projection"
         ntiles = (N + 31) // 32
         pst = K.part_stride(M1, M2)
         E1 = torch.empty(B, N, **f32)
@@ -378,8 +389,12 @@ class FreeRunningDecoder:
                 convb=P[f"{a1}/location_conv/bias"] if att1_fwd else None,
                 locW=P[f"{a1}/location_layer/kernel"] if att1_fwd else None,
                 v2=P[f"{a2}/attention_v"], e1=E1, e2=E2, part=PART, part_stride=pst,
-                s_out=S1[t + 1], a_out=AL1[t + 1], s2_out=S2[t], ctx=REC0[t + 1], ctx_sb=RX,
-                stats=None, loc_out=None)
+                s_out=SMX1 if cum else S1[t + 1], a_out=AL1[t + 1], s2_out=S2[t],
+                ctx=REC0[t + 1], ctx_sb=RX, stats=None, loc_out=None,
+                u_prev=None if U1 is None else U1[t], u_out=U1[t + 1] if agent else None,
+                agent_w=P[f"{tf_}/kernel"] if agent else None,
+                agent_b=P[f"{tf_}/bias"] if agent else None,
+                state_out=S1[t + 1] if cum else None)
 
         def lstm_stack(t, cur, nxt):
             # LSTM1 on [h0'_t | c1_t c2_t | h1_{t-1}] and LSTM2 on [h1'_t | h2_{t-1}], each one
@@ -436,6 +451,8 @@ class FreeRunningDecoder:
         for t in pl.zero_each_run:
             t.zero_()
         pl.AL1[0, :, 0] = 1.0                                 # forward_attention.py:131-133
+        if pl.U1 is not None:
+            K.fill_(pl.U1, 0.5)                               # forward_attention.py:135
         pl.state.fill_(-1)
         pl.lengths.copy_(batch["source_length"])
         K.transpose(P["decoder/attention1/query_layer/kernel"], pl.QT[:d.d1])

@@ -734,6 +734,14 @@ def attn_step_bwd(**kw):
     _lib.check(_lib.load().sat_attn_step_bwd(ctypes.byref(a), _stream()), "sat_attn_step_bwd")
 
 
+def attn_agent_bwd(**kw):
+    """sat_attn_agent_bwd: dz_t of the transition agent and its injection into dctx / dq."""
+    a = _lib.SatAttnAgentBwd()
+    for k, v in kw.items():
+        setattr(a, k, _p(v) if isinstance(v, torch.Tensor) else v)
+    _lib.check(_lib.load().sat_attn_agent_bwd(ctypes.byref(a), _stream()), "sat_attn_agent_bwd")
+
+
 def pg_stride(D1, D2, F, KW) -> int:
     return _lib.load().sat_attn_pg_stride(D1, D2, F, KW)
 

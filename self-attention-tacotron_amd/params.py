@@ -65,6 +65,9 @@ class Dims:
     num_speakers: int
     spk_dim: int
     spk_offset: int
+    # ForwardAttention options of source 1 (modules/forward_attention.py:56-57; hparams.py:113,116)
+    transition_agent: bool = False
+    cumulative_weights: bool = False
 
 
 def resolve_dims(hp) -> Dims:
@@ -78,9 +81,6 @@ def resolve_dims(hp) -> Dims:
         if a not in ("forward", "additive"):
             raise NotImplementedError(
                 f"attention '{a}' is outside the hot path (SURVEY.md section 2 row 5)")
-    if hp.cumulative_weights or hp.use_forward_attention_transition_agent:
-        raise NotImplementedError("cumulative_weights / transition agent are not used by the "
-                                  "shipped self-attention configs")
     if hp.use_external_speaker_embedding or hp.use_accent_type:
         raise NotImplementedError("external speaker / accent embeddings are out of scope")
     if getattr(hp, "code_loss_type", "l1") != "l1":
@@ -116,6 +116,11 @@ def resolve_dims(hp) -> Dims:
         multi_speaker=bool(hp.use_speaker_embedding and hp.speaker_embedd_to_prenet),
         num_speakers=hp.num_speakers, spk_dim=hp.speaker_embedding_dim,
         spk_offset=hp.speaker_embedding_offset,
+        # only ForwardAttention reads the two options (BahdanauAttention ignores them,
+        # modules/attentions.py:53-57)
+        transition_agent=bool(hp.use_forward_attention_transition_agent
+                              and hp.attention == "forward"),
+        cumulative_weights=bool(hp.cumulative_weights and hp.attention == "forward"),
     )
 
 
@@ -127,7 +132,7 @@ def _dense(out: List[ParamSpec], scope: str, fan_in: int, fan_out: int, bias: bo
 
 
 def _attention(out: List[ParamSpec], scope: str, kind: str, mem: int, query: int, units: int,
-               loc_k: int, loc_f: int) -> None:
+               loc_k: int, loc_f: int, transition_agent: bool = False) -> None:
     # BahdanauAttention memory/query layers: Dense(num_units, use_bias=False)
     _dense(out, f"{scope}/memory_layer", mem, units, bias=False)
     _dense(out, f"{scope}/query_layer", query, units, bias=False)
@@ -138,6 +143,9 @@ def _attention(out: List[ParamSpec], scope: str, kind: str, mem: int, query: int
         out.append(ParamSpec(f"{scope}/location_conv/kernel", (loc_k, 1, loc_f)))
         out.append(ParamSpec(f"{scope}/location_conv/bias", (loc_f,), "zeros"))
         _dense(out, f"{scope}/location_layer", loc_f, units, bias=False)
+        if transition_agent:
+            # :80-86 Dense(1, use_bias=True, sigmoid) over [context | processed_query] (:113)
+            _dense(out, f"{scope}/transition_factor_projection", mem + units, 1)
     else:
         # TF _bahdanau_score: attention_v [num_units], no bias (normalize=False)
         out.append(ParamSpec(f"{scope}/attention_v", (units,)))
@@ -209,7 +217,8 @@ def param_specs(hp) -> List[ParamSpec]:
             w = u
     p_last = w
     _dense(s, "decoder/attention_lstm", p_last + d.m1 + d.m2 + d.att_rnn, 4 * d.att_rnn)
-    _attention(s, "decoder/attention1", d.att1, d.m1, d.att_rnn, d.d1, d.loc_k, d.loc_f)
+    _attention(s, "decoder/attention1", d.att1, d.m1, d.att_rnn, d.d1, d.loc_k, d.loc_f,
+               transition_agent=d.transition_agent)
     _attention(s, "decoder/attention2", d.att2, d.m2, d.att_rnn, d.d2, d.loc_k, d.loc_f)
     _dense(s, "decoder/lstm1", d.att_rnn + d.m1 + d.m2 + d.dec, 4 * d.dec)
     _dense(s, "decoder/lstm2", d.dec + d.dec, 4 * d.dec)
