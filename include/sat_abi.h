@@ -915,6 +915,22 @@ int sat_exchange_pack(const int32_t* health, int32_t n_health, float* bn, int64_
                       float* tail, float bn_scale, void* stream);
 int sat_exchange_unpack(const float* tail, int32_t n_health, int32_t* health, void* stream);
 
+/* Device digest of an arena (checkpoints, sat_amd/checkpoint.py; the Estimator's Saver of
+ * train.py:67-79 has no such check).  buf is read as n_words 32-bit words w[i]:
+ *   out[0] += sum_i mix(base_index + i, w[i])               (mod 2^64)
+ *   out[1] += #{ i : (w[i] & 0x7F800000) == 0x7F800000 }    when count_nonfinite != 0
+ * with, in uint64 arithmetic,
+ *   mix(p, w):  z = ((p + 1) * 0x9E3779B97F4A7C15) ^ w;
+ *               z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *               z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *               return z ^ (z >> 31);
+ * (the splitmix64 finaliser; checkpoint.digest_host is the numpy restatement).  An integer sum:
+ * exact and independent of grid size and block order.  The caller zeroes out[] (sat_fill32);
+ * base_index chains several buffers into one digest.  buf 4-byte aligned, out 8-byte aligned,
+ * n_words == 0 is a no-op. */
+int sat_arena_digest(const void* buf, int64_t n_words, int64_t base_index,
+                     int32_t count_nonfinite, uint64_t* out, void* stream);
+
 /* ---------------------------------------------------------------- dataset records (host)
  * TFRecord framing of the dataset path: datasets/ljspeech/dataset.py:96-112 reads
  * tf.data.TFRecordDataset files written by preprocess/ljspeech.py:23-45 (utils/tfrecord.py:46-49).

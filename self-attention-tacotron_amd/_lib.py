@@ -269,6 +269,7 @@ SIGNATURES.update({
                       _P, _P],
     "sat_exchange_pack": [_P, _I32, _P, _I64, _P, _F, _P],
     "sat_exchange_unpack": [_P, _I32, _P, _P],
+    "sat_arena_digest": [_P, _I64, _I64, _I32, _P, _P],
 })
 
 RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),

@@ -33,6 +33,26 @@ def broadcast_params(flat: torch.Tensor, group=None, src: int = 0) -> None:
         tdist.broadcast(flat, src, group=group)
 
 
+def all_agree(ok: bool, device, group=None) -> bool:
+    """True iff ``ok`` holds on every rank: ONE MIN all-reduce of a flag that every rank enters
+    (nothing in a one-rank world).  Used wherever ranks must take the same branch around later
+    collectives (checkpoint restore)."""
+    if world_size(group) == 1:
+        return bool(ok)
+    t = torch.tensor([1 if ok else 0], dtype=torch.int32, device=device)
+    tdist.all_reduce(t, op=tdist.ReduceOp.MIN, group=group)
+    return bool(int(t.item()))
+
+
+def from_rank0(obj, group=None):
+    """Rank 0's (small, picklable) ``obj`` on every rank: ONE broadcast every rank enters."""
+    if world_size(group) == 1:
+        return obj
+    box = [obj]
+    tdist.broadcast_object_list(box, src=0, group=group)
+    return box[0]
+
+
 def grad_scale(group=None) -> float:
     """Factor the optimiser applies to the SUM-reduced gradient arena."""
     return 1.0 / world_size(group)

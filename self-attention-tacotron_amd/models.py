@@ -32,6 +32,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import checkpoint as C
 from . import dp
 from . import params as PR
 from .engine import Tacotron
@@ -59,6 +60,11 @@ MelData = namedtuple(
                 "binary_loss_mask"])
 EstimatorSpec = namedtuple("EstimatorSpec", ["mode", "loss", "train_op", "predictions",
                                              "eval_metric_ops"])
+# tf.estimator.WarmStartSettings as train.py:75-77 builds it: a checkpoint (file, or a directory
+# whose newest checkpoint is taken) and the regexes of the variables to initialise from it
+WarmStartSettings = namedtuple("WarmStartSettings",
+                               ["ckpt_to_initialize_from", "vars_to_warm_start"],
+                               defaults=((".*",),))
 
 
 class SelfAttentionCBHGEncoder:
@@ -188,9 +194,16 @@ class DualSourceSelfAttentionTacotronModel:
         self.params = params
         self.model_dir = model_dir
         self.config = config
-        if warm_start_from is not None:
-            raise NotImplementedError("warm start from TF checkpoints is outside the hot path")
         self.engine = Tacotron(params, device, seed=seed, init_values=init_values)
+        self._pending = None                 # a restored checkpoint whose optimiser state waits
+        self._state_path = None              # the file the current state equals (None: trained on)
+        self._host_step = 0
+        self._pending_rank0_only = False
+        # rank 0's view of model_dir decides for every replica (ONE broadcast every rank enters)
+        newest = dp.from_rank0(C.latest_checkpoint(model_dir) if model_dir else None)
+        if warm_start_from is not None and newest is None:
+            # as an Estimator: warm start only where model_dir holds no checkpoint to resume
+            self._warm_start(warm_start_from)
         # data-parallel replicas start from rank 0's weights and statistics
         dp.broadcast_params(self.engine.params)
         dp.broadcast_params(self.engine.bn.buf)
@@ -202,8 +215,119 @@ class DualSourceSelfAttentionTacotronModel:
         self.graph_t_quantum = int(env("SAT_GRAPH_T_QUANTUM", "0") if graph_t_quantum is None
                                    else graph_t_quantum)
         # dropout / zoneout masks differ per replica (each rank's shard is its own batch)
-        self._seed = seed + 1000003 * dp.rank()
+        self._seed_offset = 1000003 * dp.rank()
+        self._seed = seed + self._seed_offset
         self._eval_decoder = None
+        if newest is not None:
+            self.restore(newest)
+
+    # ---- checkpoints (checkpoint.py)
+    def _run_option(self, name):
+        cfg = self.config
+        v = cfg.get(name) if isinstance(cfg, dict) else getattr(cfg, name, None)
+        return getattr(self.params, name, None) if v is None else v
+
+    def _warm_start(self, ws) -> None:
+        """TF warm start: only the ``var/*`` tensors matched by ``vars_to_warm_start`` are
+        taken from the file; no moments, no BatchNorm statistics, the step stays 0."""
+        if not isinstance(ws, WarmStartSettings):
+            ws = WarmStartSettings(os.fspath(ws))
+        if dp.world_size() > 1:
+            # rank 0 alone reads the file (it may be the only rank that sees it); the broadcast
+            # of the parameter arena that follows construction's warm start carries the values.
+            # Its verdict is agreed on first, so a bad file raises on every rank.
+            err = None
+            if dp.rank() == 0:
+                try:
+                    self._warm_start_local(ws)
+                except (C.CheckpointError, OSError) as e:
+                    err = f"{type(e).__name__}: {e}"
+            err = dp.from_rank0(err)
+            if err is not None:
+                raise C.CheckpointError(f"warm start failed on rank 0: {err}")
+            return
+        self._warm_start_local(ws)
+
+    def _warm_start_local(self, ws) -> None:
+        path = ws.ckpt_to_initialize_from
+        if os.path.isdir(path):
+            newest = C.latest_checkpoint(path)
+            if newest is None:
+                C._refuse_tf(path)
+                raise C.CheckpointError(f"{path}: no checkpoint to warm-start from")
+            path = newest
+        sl = C.StateLayout(self.params, self.engine.layout)
+        picked = C.load_warm_start(path, sl, ws.vars_to_warm_start)
+        for name, a in picked.items():
+            self.engine.P[name].copy_(torch.from_numpy(
+                np.ascontiguousarray(PR.to_internal(name, a))))
+
+    def restore(self, path) -> None:
+        """Load ``path`` into the existing arenas (addresses unchanged, captured steps stay
+        valid).  Without a Trainer the optimiser state stays pending until the first TRAIN
+        step.  A failed load raises ``CheckpointError`` and leaves the model untouched.
+
+        Under data parallelism every rank calls this and every rank issues the same
+        collectives: with a Trainer those of ``Trainer.restore``; without one a MIN all-reduce
+        of "I can see the file", a MIN all-reduce of "my load succeeded" (any failure raises on
+        every rank, nothing written) and, where not every rank sees the file, two
+        ``dp.broadcast_params`` (parameters, BN statistics) from rank 0, whose optimiser state
+        follows the same way when the Trainer is made."""
+        path = os.fspath(path)
+        if self._trainer is not None:
+            self._trainer.restore(path, seed_offset=self._seed_offset)
+            self._pending = None
+        else:
+            dev = self.engine.device
+            sl = C.StateLayout(self.params, self.engine.layout)
+            rank0_only = not dp.all_agree(os.path.exists(path), dev)
+            ck = stage = err = None
+            if not rank0_only or dp.rank() == 0:
+                try:
+                    ck = C.load(path, sl)
+                    stage = C.stage_verified(ck, sl, dev)
+                except C.CheckpointError as e:
+                    err = e
+            if not dp.all_agree(err is None, dev):
+                raise err if err is not None else C.CheckpointError(
+                    "restore: another rank could not load the checkpoint; nothing was written")
+            if stage is not None:
+                self.engine.params.copy_(stage[:sl.n_p])
+                self.engine.bn.buf.copy_(stage[sl.o_bn:sl.o_bn + sl.n_bn])
+            if rank0_only:
+                dp.broadcast_params(self.engine.params)
+                dp.broadcast_params(self.engine.bn.buf)
+            self._pending = ck if ck is not None else True
+            self._pending_rank0_only = rank0_only
+        # whatever caches a transform of the weights is rebuilt from the restored ones
+        self._eval_decoder = None
+        self._host_step = int(dp.from_rank0(
+            C.read_meta(path)["global_step"] if dp.rank() == 0 else None))
+        self._state_path = path
+
+    def save(self, path=None):
+        """Synchronous checkpoint of the training state (``model_dir``'s next file by default)."""
+        tr = self._trainer
+        if tr is None:
+            raise C.CheckpointError("save: no training state yet (run a TRAIN step first)")
+        tr.snapshot(self.model_dir, self._run_option("keep_checkpoint_max"), path=path)
+        out = tr.wait()
+        self._state_path = out
+        return out
+
+    def _restore_for(self, checkpoint_path) -> None:
+        """EVAL / PREDICT as an Estimator: the named file, else model_dir's newest."""
+        if self._trainer is not None:
+            self._trainer.wait()
+        path = checkpoint_path
+        if path is None and self.model_dir:
+            path = C.latest_checkpoint(self.model_dir)
+        path = None if path is None else os.fspath(path)
+        # rank 0's decision holds for every replica (ONE broadcast every rank enters): either
+        # all ranks restore, and meet in restore()'s collectives, or none does
+        path, do = dp.from_rank0((path, path is not None and path != self._state_path))
+        if do:
+            self.restore(path)
 
     @staticmethod
     def learning_rate_decay(init_rate, global_step, step_factor):
@@ -236,6 +360,12 @@ class DualSourceSelfAttentionTacotronModel:
         Tp = batch["mel"].shape[1] // self.params.outputs_per_step
         if self._trainer is None:
             self._trainer = Trainer(self.engine, B, N, Tp, seed=self._seed)
+            if self._pending is not None:
+                # optimiser state, step, seed and status of the restore made before any TRAIN
+                ck, self._pending = self._pending, None
+                self._trainer.restore(ck if ck is not True else None,
+                                      seed_offset=self._seed_offset,
+                                      rank0_only=self._pending_rank0_only)
         return self._trainer
 
     def _predict(self, features) -> EstimatorSpec:
@@ -356,6 +486,8 @@ class DualSourceSelfAttentionTacotronModel:
             if self._graphs is None:
                 self._graphs = StepGraphCache(tr, self.graph_cache, self.graph_t_quantum)
             out = self._graphs.step(batch)
+            self._host_step += 1
+            self._state_path = None
             return EstimatorSpec(mode, loss=out["loss"], train_op=tr.global_step,
                                  predictions=None, eval_metric_ops=None)
         if mode == ModeKeys.EVAL:
@@ -363,19 +495,37 @@ class DualSourceSelfAttentionTacotronModel:
         raise ValueError(f"Unknown mode: {mode}")
 
     # ---- tf.estimator.Estimator-like drivers
-    def predict(self, input_fn):
+    def predict(self, input_fn, checkpoint_path=None):
+        """``checkpoint_path`` (predict_mel.py:67-68) or model_dir's newest file is restored
+        before the first batch."""
+        self._restore_for(checkpoint_path)
         for features, _ in input_fn():
             yield self.model_fn(features, None, ModeKeys.PREDICT, self.params).predictions
 
     def train(self, input_fn, steps: int):
+        """With a ``model_dir``: a snapshot whenever the step count reaches a multiple of
+        ``save_checkpoints_steps`` (queued, the loop does not wait for it) and a last one at the
+        end, which is waited for; ``keep_checkpoint_max`` files are kept."""
         loss = None
         it = iter(input_fn())
+        every = int(self._run_option("save_checkpoints_steps") or 0) if self.model_dir else 0
+        keep = self._run_option("keep_checkpoint_max")
+        saved_at = None
         for _ in range(steps):
             features, labels = next(it)
             loss = self.model_fn(features, labels, ModeKeys.TRAIN, self.params).loss
+            if every > 0 and self._host_step % every == 0:
+                self._trainer.snapshot(self.model_dir, keep)
+                saved_at = self._host_step
+        if self.model_dir and self._trainer is not None:
+            self._trainer.wait()
+            if saved_at != self._host_step and steps > 0:
+                self._trainer.snapshot(self.model_dir, keep)
+            self._state_path = self._trainer.wait()      # rank 0: the file; others: None
         return loss
 
-    def evaluate(self, input_fn, steps: int = 1):
+    def evaluate(self, input_fn, steps: int = 1, checkpoint_path=None):
+        self._restore_for(checkpoint_path)
         tot = 0.0
         it = iter(input_fn())
         for _ in range(steps):

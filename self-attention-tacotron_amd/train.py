@@ -79,6 +79,7 @@ class Trainer:
         self._comm = (torch.cuda.Stream(device=dev) if torch.device(dev).type == "cuda"
                       and self.bucketed else None)
         self._bucket_done = None
+        self._snapshotter = None             # checkpoint.Snapshotter, made on first use
 
     def reshape(self, B: int, N: int, Tp: int) -> None:
         """Point the mask views at a (B, N, T') batch shape."""
@@ -182,6 +183,74 @@ class Trainer:
             raise _lib.SatLibraryError(
                 f"{int(self._mirror[0])} training step(s) skipped by the health guard "
                 f"(first error code {int(self._mirror[1])})")
+
+    # ---- checkpoints (checkpoint.py): snapshot between steps, restore in place
+    def _snap(self):
+        if self._snapshotter is None:
+            from .checkpoint import Snapshotter
+            self._snapshotter = Snapshotter(self)
+        return self._snapshotter
+
+    def snapshot(self, model_dir: Optional[str] = None, keep_max: Optional[int] = None,
+                 path: Optional[str] = None, force_exchange: bool = False) -> None:
+        """Queue a checkpoint of the current state (between steps, outside any capture): copies
+        into the staging arena and their digest on the current stream, the host copy on a side
+        stream, the file by the writer thread.  Does not wait for the device.  Raises what the
+        previous snapshot found (non-finite values, skipped steps, replicas that differ, an I/O
+        error); with ``world > 1`` every rank calls it (rank 0 writes)."""
+        self._snap().snapshot(model_dir, keep_max, path, force_exchange)
+
+    def wait(self) -> Optional[str]:
+        """Block until the pending snapshot is on disk; returns its path."""
+        return None if self._snapshotter is None else self._snapshotter.wait()
+
+    def save(self, path: str) -> Optional[str]:
+        self.snapshot(path=path)
+        return self.wait()
+
+    def restore(self, path, seed_offset: int = 0, rank0_only: Optional[bool] = None) -> None:
+        """Load a checkpoint (a path, or a ``checkpoint.Loaded``) into the EXISTING arenas with
+        ``copy_``: every captured graph stays valid and replays on the restored state.  The file
+        is validated on the host and its digest recomputed on the device before a live tensor is
+        written.  ``seed_offset`` is added to the file's seed (rank 0's; replicas draw different
+        masks).
+
+        With ``world > 1`` every rank calls this, and every rank issues the same collectives
+        whatever it finds: (1) a MIN all-reduce of "I can see the file" (skipped when the caller
+        passes ``rank0_only``, having agreed on it already); (2) a MIN all-reduce of "my load
+        and device digest succeeded" -- if any rank failed, every rank raises and no arena is
+        written; (3) where not every rank sees the file, rank 0 loads alone and seven
+        ``dp.broadcast_params`` carry parameters, moments, BN statistics, step, seed and
+        status."""
+        import os
+        from . import checkpoint as C
+        snap = self._snap()
+        dev = self.m.device
+        if self.world == 1:
+            rank0_only = False
+        elif rank0_only is None:
+            rank0_only = not dp.all_agree(isinstance(path, C.Loaded) or os.path.exists(path),
+                                          dev, self.pg)
+        loads = not rank0_only or dp.rank(self.pg) == 0
+        err = None
+        if loads:
+            try:
+                ck = path if isinstance(path, C.Loaded) else C.load(path, snap.sl)
+                snap.upload_verified(ck)
+            except C.CheckpointError as e:
+                err = e
+        if not dp.all_agree(err is None, dev, self.pg):
+            raise err if err is not None else C.CheckpointError(
+                "restore: another rank could not load the checkpoint; nothing was written")
+        if loads:
+            snap.apply_stage()
+        if rank0_only:
+            for t in (self.m.params, self.exp_avg, self.exp_avg_sq, self.m.bn.buf,
+                      self.global_step, self.seed, self.status):
+                dp.broadcast_params(t, self.pg)
+        if seed_offset:
+            self.seed.add_(int(seed_offset))
+        self._mirror_evt = None              # the mirror described the state before the restore
 
     def step(self, batch):
         self.check_health()
