@@ -41,8 +41,9 @@ extern "C" {
  * with Lq / causal, SatMha.lse); 6: SatMha.wgrad_stream / wgrad_ws; 7: SatAttnParamGrad.tsplit; 8: SatMha without
  * wgrad_stream / wgrad_ws (deferred weight gradients: sat_mha_bwd_wgrad); 9: the transition agent
  * and cumulative weights of ForwardAttention (trailing fields of SatAttnStep / SatAttnStepBwd,
- * sat_attn_agent_bwd). */
-#define SAT_ABI_VERSION 9
+ * sat_attn_agent_bwd); 10: SatAttnStep.agent_b_sb, the speaker-vector kernels (sat_rows_bias_fwd /
+ * _bwd, sat_ctx_tail_fill). */
+#define SAT_ABI_VERSION 10
 
 /* ---------------------------------------------------------------- library */
 int sat_version(void);                         /* 100*major + minor */
@@ -447,7 +448,8 @@ int sat_lstm_steps_bwd(const SatLstmBwd* steps, int32_t n, void* stream);
  * fields; all of them NULL (a zero-initialised struct) is the plain step above:
  *   u_prev   [B] transition factor u_{t-1} per utterance, used instead of the scalar u;
  *   u_out    [B] u_t = sigmoid([c1_t | q_t[:D1]] . agent_w + agent_b) (use_transition_agent;
- *            agent_w [M1 + D1] = transition_factor_projection/kernel, agent_b [1] its bias),
+ *            agent_w [M1 + D1] = transition_factor_projection/kernel, agent_b [1] its bias, or
+ *            [B] with agent_b_sb = 1),
  *            formed by the combine kernel from the context it has just written: no extra launch.
  *            A u_out request without agent_w / agent_b is refused (SAT_ERR_ARGUMENT);
  *   state_out[B][N] = s_out + s_prev, the state the next step's location convolution reads
@@ -479,6 +481,9 @@ typedef struct SatAttnStep {
   float* u_out;                             /* [B] or NULL (no transition agent) */
   const float* agent_w; const float* agent_b; /* [M1 + D1], [1]; needed with u_out */
   float* state_out;                         /* [B][N] or NULL (state = s_out) */
+  int64_t agent_b_sb;                       /* 0: agent_b [1] shared; 1: agent_b [B], one bias per
+                                               utterance (speaker_embedd_to_decoder folds the
+                                               speaker rows of the projection into it) */
 } SatAttnStep;
 
 int sat_attn_part_stride(int32_t M1, int32_t M2);
@@ -785,6 +790,25 @@ int sat_decoder_lstms_bwd(const SatDecLstmBwd* args, void* stream);
  * out[b,n,:] = x[b,n,:] * (n < lengths[b])  -- TF _prepare_memory (memory_sequence_length). */
 int sat_seq_mask(const float* x, float* out, int32_t B, int32_t N, int32_t C,
                  const int64_t* lengths, void* stream);
+
+/* Speaker vector to the decoder (models/models.py:72-83, speaker_embedd_to_decoder): the columns
+ * the reference appends to both memories are constant over the encoder positions, so their
+ * consumers take a per-utterance bias row or the vector itself in the tail of a context row.
+ * Every pointer 16-byte aligned; C / S / col0 and every stride multiples of 4 (floats).
+ *   sat_rows_bias_fwd: y[b*y_sb + n*y_sn + c] += bias[b*bias_sb + c] for n < min(lengths[b], N),
+ *     c < C; lengths NULL = every row.  (Batch-major [B][N][C]: y_sb = N*ld, y_sn = ld; step-major
+ *     [T][B][C]: y_sb = ld, y_sn = B*ld with N = T.)
+ *   sat_rows_bias_bwd: dbias[b*dbias_sb + c] = sum_{n < min(lengths[b], N)} dy[b*dy_sb + n*dy_sn
+ *     + c] (overwritten; fp64 partial sums added in a fixed order, no atomics: bit-reproducible).
+ *   sat_ctx_tail_fill: ctx[t*ctx_st + b*ctx_sb + col0 + j] = s[b*s_sb + j] for t0 <= t < t1,
+ *     j < S (rows outside the range are left as they are: step 0's fed attention stays zero). */
+int sat_rows_bias_fwd(float* y, int64_t y_sb, int64_t y_sn, const float* bias, int64_t bias_sb,
+                      int32_t B, int32_t N, int32_t C, const int64_t* lengths, void* stream);
+int sat_rows_bias_bwd(const float* dy, int64_t dy_sb, int64_t dy_sn, float* dbias,
+                      int64_t dbias_sb, int32_t B, int32_t N, int32_t C, const int64_t* lengths,
+                      void* stream);
+int sat_ctx_tail_fill(float* ctx, int64_t ctx_st, int64_t ctx_sb, int32_t col0, const float* s,
+                      int64_t s_sb, int32_t t0, int32_t t1, int32_t B, int32_t S, void* stream);
 
 /* Embedding lookup (ext tacotron2 Embedding, models/models.py:28,54): out[r] = table[ids[r]-offset];
  * an id outside [offset, offset+V) writes zeros and sets *err = 1 (the reference's

@@ -189,7 +189,7 @@ SatAttnStep = _struct("SatAttnStep", """
     f32:u ptr:q i64:q_sb ptr:K1 ptr:V1 ptr:K2 ptr:V2 ptr:lengths ptr:s_prev ptr:a_prev
     ptr:v1 ptr:b1 ptr:convW ptr:convb ptr:locW ptr:v2 ptr:e1 ptr:e2 ptr:part i64:part_stride
     ptr:s_out ptr:a_out ptr:s2_out ptr:ctx i64:ctx_sb ptr:stats ptr:loc_out i32:lpp i32:phases
-    ptr:u_prev ptr:u_out ptr:agent_w ptr:agent_b ptr:state_out""")
+    ptr:u_prev ptr:u_out ptr:agent_w ptr:agent_b ptr:state_out i64:agent_b_sb""")
 
 # name -> argtypes (restype is int for all but sat_last_error_string)
 SIGNATURES = {
@@ -236,6 +236,9 @@ SIGNATURES = {
     "sat_attn_param_grad_rows": [_I32, _I32],
     "sat_attn_param_grads": [ctypes.POINTER(SatAttnParamGrad), _P],
     "sat_seq_mask": [_P, _P, _I32, _I32, _I32, _P, _P],
+    "sat_rows_bias_fwd": [_P, _I64, _I64, _P, _I64, _I32, _I32, _I32, _P, _P],
+    "sat_rows_bias_bwd": [_P, _I64, _I64, _P, _I64, _I32, _I32, _I32, _P, _P],
+    "sat_ctx_tail_fill": [_P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _I32, _I32, _P],
     "sat_embedding_fwd": [_P, _P, _P, _I64, _I32, _I32, _I64, _P, _P],
     "sat_embedding_bwd": [_P, _P, _P, _I64, _I32, _I32, _I64, _P],
     "sat_bn_stats": [_P, _I64, _I32, _I32, _P, _P, _P, _P, _F, _P, _P],
@@ -291,7 +294,7 @@ RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
 
 _lib: Optional[ctypes.CDLL] = None
 # include/sat_abi.h SAT_ABI_VERSION this binding's structs follow
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 def load(path: str = LIB_PATH) -> ctypes.CDLL:

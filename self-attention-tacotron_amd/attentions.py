@@ -22,6 +22,12 @@ factor ``u_t = sigmoid([context | processed_query] . w + b)``, :80-86, :111-114;
 alignments, :118-119).  Both run inside the same two launches per step; ``BahdanauAttention``
 ignores them, as in the reference.
 
+``speaker_embedd_to_decoder`` (models/models.py:77-83) needs no change here: inside the model the
+speaker columns never reach a mechanism as memory columns (decoder.py folds them into the keys as
+one bias row per utterance), so the step kernels keep their memory widths (M1 <= 256, M2 <= 32).
+A caller of this plugin surface who passes a pre-concatenated ``[memory | speaker]`` tensor wider
+than that is refused by ``sat_attn_step_fwd`` as before.
+
 Supported kinds on this path: ``"forward"`` (ForwardAttention), ``"additive"``
 (BahdanauAttention) and the forced-alignment kinds ``"teacher_forcing_forward"`` /
 ``"teacher_forcing_additive"`` (modules/teacher_forcing_attention.py:13-78: step ``index``

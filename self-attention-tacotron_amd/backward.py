@@ -213,6 +213,8 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
 
     W2, dW2 = P["decoder/lstm2/kernel"], G["decoder/lstm2/kernel"]
     W1, dW1 = P["decoder/lstm1/kernel"], G["decoder/lstm1/kernel"]
+    h1_rows = slice(A + M1 + M2, A + M1 + M2 + Dd)        # LSTM1's recurrent rows (speaker rows,
+    W1r = W1[h1_rows]                                     # when there, follow them)
     DG2 = torch.empty_like(S["G2"])
     DG1 = torch.empty_like(S["G1"])
     dH1 = torch.empty(Tp, B, Dd, **f32)
@@ -235,7 +237,7 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
                          mask_h=None if m2h is None else m2h[t], zc=zc, zh=zh, dgates=DG2[t])
 
     def lstm1_desc(t):
-        return run1.desc(B=B, U=Dd, K=Dd, hoff=0, t=t, W=W1[A + M1 + M2:],
+        return run1.desc(B=B, U=Dd, K=Dd, hoff=0, t=t, W=W1r,
                          dgates_next=DG1[t + 1] if t + 1 < Tp else None, gates=S["G1"][t],
                          c_prev=S["C1S"][t], dy=dH1[t], mask_c=None if m1c is None else m1c[t],
                          mask_h=None if m1h is None else m1h[t], zc=zc, zh=zh, dgates=DG1[t])
@@ -258,7 +260,7 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
     W0 = P["decoder/attention_lstm/kernel"]
     dW0 = G["decoder/attention_lstm/kernel"]
     p_w = S["prenet"][-1].shape[-1]
-    W0r = W0[p_w:]
+    W0r = W0[p_w:p_w + R0]
     a1, a2 = "decoder/attention1", "decoder/attention2"
     fwd = d.att1 == "forward"
     ntiles = (N + attn_tile - 1) // attn_tile
@@ -357,7 +359,7 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
         # gradients into the chain as whole-sequence GEMMs, then the attention chain's BPTT as
         # ONE persistent launch (sat_decoder_attention_bwd)
         K.decoder_lstms_bwd(
-            B=B, T=Tp, U=Dd, zc=zc, zh=zh, W1r=W1[A + M1 + M2:], W2=W2, G1=S["G1"],
+            B=B, T=Tp, U=Dd, zc=zc, zh=zh, W1r=W1r, W2=W2, G1=S["G1"],
             C1S=S["C1S"], G2=S["G2"], C2S=S["C2S"], DH2=dH2, mask1_c=m1c, mask1_h=m1h,
             mask2_c=m2c, mask2_h=m2h, DG1=DG1, DG2=DG2, ctr=scratch.lstm_ctr,
             err=scratch.lstm_err[1])
@@ -440,22 +442,22 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
             K.gemm_wgrad_batch([h1raw, h2s], DG2f, [dW2[:Dd], dW2[Dd:]],
                                colsum=G["decoder/lstm2/bias"])
             if A == Dd:
-                K.gemm_wgrad_batch([h1s, h0raw], DG1f, [dW1[A + M1 + M2:], dW1[:A]],
+                K.gemm_wgrad_batch([h1s, h0raw], DG1f, [dW1[h1_rows], dW1[:A]],
                                    colsum=G["decoder/lstm1/bias"])
             else:
-                K.gemm(h1s.t(), DG1f, dW1[A + M1 + M2:], beta=1.0, colsum=G["decoder/lstm1/bias"])
+                K.gemm(h1s.t(), DG1f, dW1[h1_rows], beta=1.0, colsum=G["decoder/lstm1/bias"])
                 K.gemm(h0raw.t(), DG1f, dW1[:A], beta=1.0)
         else:
             K.gemm(h2s.t(), DG2f, dW2[Dd:], beta=1.0)
             K.gemm(h1raw.t(), DG2f, dW2[:Dd], beta=1.0,
                    colsum=G["decoder/lstm2/bias"])                 # + the bias gradient
-            K.gemm(h1s.t(), DG1f, dW1[A + M1 + M2:], beta=1.0, colsum=G["decoder/lstm1/bias"])
+            K.gemm(h1s.t(), DG1f, dW1[h1_rows], beta=1.0, colsum=G["decoder/lstm1/bias"])
             K.gemm(h0raw.t(), DG1f, dW1[:A], beta=1.0)
         ctx_all = S["REC0"][1:].reshape(Tp * B, R0)[:, :M1 + M2]
         K.gemm(ctx_all.t(), DG1f, dW1[A:A + M1 + M2], beta=1.0)
 
         DG0f = DG0.view(Tp * B, 4 * A)
-        K.gemm(S["REC0"][:Tp].reshape(Tp * B, R0).t(), DG0f, dW0[p_w:], beta=1.0)
+        K.gemm(S["REC0"][:Tp].reshape(Tp * B, R0).t(), DG0f, dW0[p_w:p_w + R0], beta=1.0)
         dP = lin_bwd(S["prenet"][-1], DG0, W0[:p_w], dW0[:p_w], G["decoder/attention_lstm/bias"], ws)
         # decoder prenets (inputs are teacher frames: no input gradient needed for the first one)
         pres = S["prenet"]
@@ -486,7 +488,7 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
             DZf = DZ.view(Tp * B, 1)
             dwk = G[f"{tf_}/kernel"]
             K.gemm(S["REC0"][1:].reshape(Tp * B, R0)[:, :M1].t(), DZf, dwk[:M1], beta=1.0)
-            K.gemm(S["Q"].view(Tp * B, D1 + D2)[:, :D1].t(), DZf, dwk[M1:], beta=1.0,
+            K.gemm(S["Q"].view(Tp * B, D1 + D2)[:, :D1].t(), DZf, dwk[M1:M1 + D1], beta=1.0,
                    colsum=G[f"{tf_}/bias"])
 
     if not late:
@@ -521,10 +523,48 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
     # ---- memories: values via the alignment histories, keys via memory_layer
     dV1 = K.gemm(S["AL1"][1:].permute(1, 2, 0), DCTX[:, :, :M1].permute(1, 0, 2))   # [B, N, M1]
     dV2 = K.gemm(S["S2"].permute(1, 2, 0), DCTX[:, :, M1:].permute(1, 0, 2))        # [B, N, M2]
-    lin_bwd(S["V1"], dK1, P[f"{a1}/memory_layer/kernel"], G[f"{a1}/memory_layer/kernel"], None,
-            ws, dx=dV1, beta_dx=1.0)
-    lin_bwd(S["V2"], dK2, P[f"{a2}/memory_layer/kernel"], G[f"{a2}/memory_layer/kernel"], None,
-            ws, dx=dV2, beta_dx=1.0)
+    Wm1, dWm1 = P[f"{a1}/memory_layer/kernel"], G[f"{a1}/memory_layer/kernel"]
+    Wm2, dWm2 = P[f"{a2}/memory_layer/kernel"], G[f"{a2}/memory_layer/kernel"]
+    lin_bwd(S["V1"], dK1, Wm1[:M1], dWm1[:M1], None, ws, dx=dV1, beta_dx=1.0)
+    lin_bwd(S["V2"], dK2, Wm2[:M2], dWm2[:M2], None, ws, dx=dV2, beta_dx=1.0)
+    sd = S.get("spk_dec")
+    if sd is not None:
+        # ---- speaker vector appended to both memories (decoder_forward): every consumer took it
+        #      as a per-utterance bias row b = s W_s, so dW_s += s^T db and ds += db W_s^T with
+        #      db the bias row's gradient, summed over the rows it was added to.  The contexts'
+        #      tails are s itself (sum alpha = 1), so nothing here enters the attention backward.
+        s, ss = sd["s"], sd["ss"]
+        lengths = S["lengths"]
+        ds = torch.empty_like(s)
+        first = [True]
+
+        def through(db, Ws, dWs, x=s):
+            K.gemm(x.t(), db, dWs, beta=1.0)
+            nblk = Ws.shape[0] // s.shape[1]             # [s | s] row blocks: both reach s
+            for i in range(nblk):
+                K.gemm(db, Ws[i * s.shape[1]:(i + 1) * s.shape[1]].t(), ds,
+                       beta=0.0 if first[0] else 1.0)
+                first[0] = False
+        through(K.rows_bias_bwd(dK1, lengths), Wm1[M1:], dWm1[M1:])
+        through(K.rows_bias_bwd(dK2, lengths), Wm2[M2:], dWm2[M2:])
+        through(K.rows_bias_bwd(DG1, step_major=True), W1[A + M1 + M2 + Dd:],
+                dW1[A + M1 + M2 + Dd:], x=ss)
+        if Tp > 1:                                        # step 0 was fed zeros
+            through(K.rows_bias_bwd(DG0[1:], step_major=True), W0[p_w + R0:], dW0[p_w + R0:],
+                    x=ss)
+        if agent:
+            dzs = torch.empty(B, 1, **f32)
+            K.colsum(DZ, dzs.view(-1), ws, beta=0.0)      # sum over the steps of dz_t
+            through(dzs, P[f"{tf_}/kernel"][M1 + D1:], G[f"{tf_}/kernel"][M1 + D1:])
+        rec = S["speaker"]
+        if d.multi_speaker:
+            # the prenet's share was formed on the weight-gradient stream
+            ds_pre = rec.pop("ds_pre")
+            if aux is not None:
+                torch.cuda.current_stream().wait_stream(aux.s)
+                aux.keep.append(ds_pre)
+            K.axpby(ds_pre, ds, 1.0, 1.0)
+        speaker_bwd(P, G, d, rec, ds, ws)
     return dV1, dV2          # caller applies the sequence mask (values were masked memories)
 
 
@@ -541,11 +581,26 @@ def multi_speaker_prenet_bwd(P, G, d, S, ms, dd0, ws):
     K.act_bwd(dsp, ms["sp"], dspre, "softsign")
     dspk = lin_bwd(ms["spk"], dspre, P[f"{sc}/speaker_projection/kernel"],
                    G[f"{sc}/speaker_projection/kernel"], G[f"{sc}/speaker_projection/bias"], ws)
-    K.embedding_bwd(dspk, ms["ids"], G["speaker_embedding"], offset=d.spk_offset)
+    if d.spk_to_decoder:
+        S["speaker"]["ds_pre"] = dspk        # decoder_bwd adds the memories' share and finishes
+    else:
+        speaker_bwd(P, G, d, S["speaker"], dspk, ws)
     dpre0 = torch.empty_like(dd0)
     K.act_bwd(dd0, ms["y0"], dpre0, "relu")
     lin_bwd(S["xin"], dpre0, P[f"{sc}/dense0/kernel"], G[f"{sc}/dense0/kernel"],
             G[f"{sc}/dense0/bias"], ws, need_dx=False)
+
+
+def speaker_bwd(P, G, d, rec, ds, ws):
+    """Backward of model.speaker_vector: ds [B, S] through the ReLU projection (when on) into
+    the speaker-embedding rows."""
+    if d.spk_proj > -1:
+        dpre = torch.empty_like(ds)
+        K.act_bwd(ds, rec["s"], dpre, "relu")
+        ds = lin_bwd(rec["raw"], dpre, P["speaker_embedding_projection/kernel"],
+                     G["speaker_embedding_projection/kernel"],
+                     G["speaker_embedding_projection/bias"], ws)
+    K.embedding_bwd(ds, rec["ids"], G["speaker_embedding"], offset=d.spk_offset)
 
 
 def encoder_bwd(P, G, hp, d, sv, dm1, dm2, lengths, masks, ws, aux: Aux = None):

@@ -55,7 +55,8 @@ struct AttnCombineP {
   // transition agent / cumulative weights (EXT instantiation only)
   int D1;
   const float* u_prev; float* u_out;           // [B]
-  const float* agent_w; const float* agent_b;  // [M1 + D1], [1]
+  const float* agent_w; const float* agent_b;  // [M1 + D1], [1] (or [B]: agent_b_sb = 1)
+  int64_t agent_b_sb;
   const float* q; int64_t q_sb;                // processed queries (the agent reads q[:D1])
   const float* s_prev; float* state_out;       // [B][N]: state_out = s + s_prev
 };
@@ -139,7 +140,7 @@ __device__ __forceinline__ void combine_utterance(const AttnCombineP& p, int b) 
     if (lane == 0) zred[wave] = zacc;
     __syncthreads();
     if (tid == 0) {
-      const float z = (zred[0] + zred[1]) + (zred[2] + zred[3]) + p.agent_b[0];
+      const float z = (zred[0] + zred[1]) + (zred[2] + zred[3]) + p.agent_b[b * p.agent_b_sb];
       p.u_out[b] = 1.f / (1.f + expf(-z));
     }
   }
@@ -632,6 +633,7 @@ extern "C" int sat_attn_step_fwd(const SatAttnStep* a, void* stream) {
                 "sat_attn_step_fwd: u_prev / u_out / state_out need forward attention");
   SAT_CHECK_ARG(!a->u_out || (a->agent_w && a->agent_b),
                 "sat_attn_step_fwd: u_out (transition agent) needs agent_w and agent_b");
+  SAT_CHECK_ARG(a->agent_b_sb == 0 || a->agent_b_sb == 1, "sat_attn_step_fwd: agent_b_sb is 0 or 1");
   AttnFwdP p;
   p.u_prev = a->u_prev;
   p.B = a->B; p.N = a->N; p.D1 = a->D1; p.M1 = a->M1; p.D2 = a->D2; p.M2 = a->M2;
@@ -683,7 +685,7 @@ extern "C" int sat_attn_step_fwd(const SatAttnStep* a, void* stream) {
   c.a_prev = a->a_prev; c.s_out = a->s_out; c.a_out = a->a_out; c.s2_out = a->s2_out;
   c.ctx = a->ctx; c.ctx_sb = a->ctx_sb; c.stats = a->stats;
   c.D1 = a->D1; c.u_prev = a->u_prev; c.u_out = a->u_out; c.agent_w = a->agent_w;
-  c.agent_b = a->agent_b; c.q = a->q; c.q_sb = a->q_sb; c.s_prev = a->s_prev;
+  c.agent_b = a->agent_b; c.agent_b_sb = a->agent_b_sb; c.q = a->q; c.q_sb = a->q_sb; c.s_prev = a->s_prev;
   c.state_out = a->state_out;
   if (ext) hipLaunchKernelGGL(attn_combine_kernel<true>, dim3(a->B), dim3(256), 0, s, c);
   else hipLaunchKernelGGL(attn_combine_kernel<false>, dim3(a->B), dim3(256), 0, s, c);

@@ -116,6 +116,10 @@ def persistent_ineligible_reason(d: Dims, B: int, N: int, attn_tile: int = 32) -
     if d.cumulative_weights:
         return ("cumulative_weights=True: the persistent kernels convolve the plain softmax "
                 "state")
+    # speaker_embedd_to_decoder stays eligible: every consumer of the appended speaker columns
+    # is a bias row of a term hoisted out of the recurrence (keys, X0, X1), formed before the
+    # persistent launches; only the transition agent reads it inside a step, and the agent is
+    # refused above
     if attn_tile != 32:
         return f"attn_tile {attn_tile} != 32"
     dims = (d.att_rnn, d.m1, d.m2, d.d1, d.d2, d.loc_f, d.loc_k, d.dec)
@@ -163,7 +167,8 @@ def use_persistent(d: Dims, B: int, N: int, attn_tile: int = 32, persistent: boo
 def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m2: torch.Tensor,
                     lengths: torch.Tensor, targets: torch.Tensor,
                     masks: Optional[Dict[str, torch.Tensor]], attn_tile: int = 32,
-                    spk: Optional[torch.Tensor] = None, pipe: Pipeline = SEQUENTIAL,
+                    spk: Optional[torch.Tensor] = None,
+                    spk_dec: Optional[torch.Tensor] = None, pipe: Pipeline = SEQUENTIAL,
                     persistent: bool = False, scratch=None, keep_tanh: bool = True,
                     inputs: Optional[Dict[str, object]] = None):
     """Forward of the teacher-forced decoder; returns (D [T', B, dec], DecoderSaved).
@@ -173,7 +178,11 @@ def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m
     then the two decoder LSTMs as a two-problem wavefront; otherwise the per-step launches.
     ``keep_tanh`` keeps the energies' tanh for the persistent BPTT (off for inference).
     ``inputs``: the teacher frames, prenets and attention-RNN input projection already formed
-    by ``decoder_inputs`` (model_forward runs them on a second stream beside the encoder)."""
+    by ``decoder_inputs`` (model_forward runs them on a second stream beside the encoder).
+    ``spk``: the speaker vector for the prenet; ``spk_dec`` [B, S]: the speaker vector the
+    reference appends to both memories (speaker_embedd_to_decoder).  Its columns are constant
+    over the positions, so it enters as per-utterance bias rows of the keys and of the two
+    hoisted input projections (and of the transition agent), DESIGN.md section 5d."""
     dev = m1.device
     B, N, _ = m1.shape
     r, nf = d.r, hp.n_feed_frame
@@ -188,9 +197,22 @@ def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m
     # ---- memories (TF _prepare_memory + memory_layer), once per utterance
     V1 = K.seq_mask(m1, lengths)
     V2 = K.seq_mask(m2, lengths)
-    K1 = K.linear(V1, P["decoder/attention1/memory_layer/kernel"])
-    K2 = K.linear(V2, P["decoder/attention2/memory_layer/kernel"])
-    S.update(V1=V1, V2=V2, K1=K1, K2=K2)
+    Wm1 = P["decoder/attention1/memory_layer/kernel"]       # [M1 (+ S), D1]
+    Wm2 = P["decoder/attention2/memory_layer/kernel"]
+    K1 = K.linear(V1, Wm1[:M1])
+    K2 = K.linear(V2, Wm2[:M2])
+    S.update(V1=V1, V2=V2, K1=K1, K2=K2, lengths=lengths)
+    ss = None
+    if spk_dec is not None:
+        # memory_layer([V | s]) = V W[:M] + s W[M:]: one row per utterance on the unmasked
+        # positions (masked values give zero keys)
+        K.rows_bias_fwd(K1, K.linear(spk_dec, Wm1[M1:]), lengths)
+        K.rows_bias_fwd(K2, K.linear(spk_dec, Wm2[M2:]), lengths)
+        # [s | s] against the two trailing speaker row blocks of the LSTM kernels
+        Sw = spk_dec.shape[1]
+        ss = torch.empty(B, 2 * Sw, **f32)
+        K.copy3d_(ss.view(B, 2, Sw), spk_dec.unsqueeze(1).expand(B, 2, Sw))
+        S["spk_dec"] = dict(s=spk_dec, ss=ss)
 
     # ---- prenets over all frames (teacher forcing), dropout fused as a multiplicative epilogue
     xin = teacher_inputs(targets, r, nf) if inputs is None else inputs["xin"]
@@ -228,6 +250,10 @@ def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m
     X0 = (K.linear(pre, W0[:p_w], P["decoder/attention_lstm/bias"]) if inputs is None
           else inputs["X0"])                         # [T', B, 4A]
     R0 = M1 + M2 + A                                 # recurrent input [c1 | c2 | h0]
+    if ss is not None and Tp > 1:
+        # the contexts fed from step 1 on end in s (the alignments sum to one); step 0 is fed
+        # zeros, tail included
+        K.rows_bias_fwd(X0[1:], K.linear(ss, W0[p_w + R0:]), step_major=True)
     # zero-initialised state histories (row 0 = initial state), one fill for all of them and
     # for the decoder LSTMs' c / h histories below
     hist = inputs.get("hist") if inputs is not None else None
@@ -262,7 +288,11 @@ def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m
     U1 = K.fill_(torch.empty(Tp + 1, B, **f32), 0.5) if agent or cum else None
     SM1 = torch.empty(Tp, B, N, **f32) if cum else None
     tf_ = f"{a1}/transition_factor_projection"
-    Wr0 = W0[p_w:]
+    agent_b = P[f"{tf_}/bias"] if agent else None
+    if agent and spk_dec is not None:
+        # [c1 | s | pq] . w: the speaker rows (kept last) fold into one bias per utterance
+        agent_b = K.linear(spk_dec, P[f"{tf_}/kernel"][M1 + D1:], agent_b)          # [B, 1]
+    Wr0 = W0[p_w:p_w + R0]
     # query layers of both mechanisms, transposed once per step so the per-decoder-step query
     # product is a skinny row-dot ([B, A] x [D1+D2, A]^T)
     # (made on first use: the persistent path reads the kernels directly)
@@ -299,11 +329,14 @@ def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m
             ctx=REC0[t + 1], ctx_sb=R0, stats=ST[t], loc_out=None if LOC is None else LOC[t],
             u_prev=None if U1 is None else U1[t], u_out=U1[t + 1] if agent else None,
             agent_w=P[f"{tf_}/kernel"] if agent else None,
-            agent_b=P[f"{tf_}/bias"] if agent else None,
+            agent_b=agent_b, agent_b_sb=1 if agent and spk_dec is not None else 0,
             state_out=S1[t + 1] if cum else None)
 
     # ---- decoder LSTM 1: input o_t = [h0'_t | c1_t | c2_t]  (ConcatOutputAndAttentionWrapper)
-    W1 = P["decoder/lstm1/kernel"]                   # [A + M1 + M2 + D, 4D]
+    W1 = P["decoder/lstm1/kernel"]                   # [A + M1 + M2 + D (+ 2S), 4D]
+    W1r = W1[A + M1 + M2:A + M1 + M2 + Dd]
+    # LSTM1 reads the contexts of its own step: the speaker tail is there at every step
+    b1s = K.linear(ss, W1[A + M1 + M2 + Dd:]) if ss is not None else None
     W2 = P["decoder/lstm2/kernel"]                   # [D + D, 4D]
     X1 = torch.empty(Tp, B, 4 * Dd, **f32)
     X2 = torch.empty(Tp, B, 4 * Dd, **f32)
@@ -319,6 +352,8 @@ def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m
         # (REC0 row t+1) are the two A segments of W1x
         K.gemm(H0RAW[a:b].reshape(n, A), W1[:A + M1 + M2], x1, bias=P["decoder/lstm1/bias"],
                A2=REC0[a + 1:b + 1].reshape(n, R0)[:, :M1 + M2])
+        if b1s is not None:
+            K.rows_bias_fwd(X1[a:b], b1s, step_major=True)
 
     def x2_chunk(a, b):
         n = (b - a) * B
@@ -326,7 +361,7 @@ def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m
                  out=X2[a:b].view(n, 4 * Dd))
 
     def lstm1_desc(t):
-        return _lstm_desc(X1, W1[A + M1 + M2:], t, B, Dd, zc, zh, m1c, m1h, L1)
+        return _lstm_desc(X1, W1r, t, B, Dd, zc, zh, m1c, m1h, L1)
 
     def lstm2_desc(t):
         return _lstm_desc(X2, W2[Dd:], t, B, Dd, zc, zh, m2c, m2h, L2)
@@ -356,7 +391,7 @@ def decoder_forward(P: Dict[str, torch.Tensor], hp, d: Dims, m1: torch.Tensor, m
         x1_chunk(0, Tp)
         X2 = None
         K.decoder_lstms_fwd(
-            B=B, T=Tp, U=Dd, zc=zc, zh=zh, X1=X1, W1r=W1[A + M1 + M2:], W2=W2,
+            B=B, T=Tp, U=Dd, zc=zc, zh=zh, X1=X1, W1r=W1r, W2=W2,
             b2=P["decoder/lstm2/bias"], mask1_c=m1c, mask1_h=m1h, mask2_c=m2c, mask2_h=m2h,
             H1RAW=L1[0], C1S=L1[1], H1S=L1[2], G1=L1[3], H2RAW=L2[0], C2S=L2[1], H2S=L2[2],
             G2=L2[3], xch=scratch.lstm_xch, err=scratch.lstm_err[0])

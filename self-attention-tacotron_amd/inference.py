@@ -54,7 +54,7 @@ import torch
 
 from . import _lib
 from . import kernels as K
-from .model import BNState, encoder_fwd
+from .model import BNState, encoder_fwd, speaker_vector
 from .params import Dims
 
 
@@ -143,6 +143,9 @@ class FreeRunningDecoder:
         for k, v in dims.items():
             if getattr(d, k) != v:
                 return f"{k}={getattr(d, k)!r}, needs {v!r}"
+        if d.spk_to_decoder:
+            # sat_decode_persistent has no per-utterance input rows for the speaker terms
+            return "speaker_embedd_to_decoder is on the per-step path only"
         if d.transition_agent or d.cumulative_weights:
             # sat_decode_persistent carries a scalar u and the plain softmax state
             return ("use_forward_attention_transition_agent / cumulative_weights are on the "
@@ -286,9 +289,18 @@ class FreeRunningDecoder:
         MELC = torch.empty(B, M * r, **f32)                 # contiguous copy for that feedback
         # the attention RNN's whole input row per step: [prenet out (p_w) | c1 | c2 | h0], so its
         # product (input projection included) is ONE step launch against the full kernel W0
+        # With speaker_embedd_to_decoder the row ends in [s | s] from step 1 on (the tails of the
+        # two contexts, sat_ctx_tail_fill; row 0, the zero attention fed at step 0, keeps zeros),
+        # against the kernel's trailing speaker rows.
+        Sd = d.spk_width if d.spk_to_decoder else 0
         RX = p_w + R0
-        pl.REC0X = REC0X = torch.zeros(Tm + 1, B, RX, **f32)
-        pl.REC0 = REC0 = REC0X[..., p_w:]                  # [c1 | c2 | h0] per step (view)
+        RXW = RX + 2 * Sd
+        pl.REC0X = REC0X = torch.zeros(Tm + 1, B, RXW, **f32)
+        pl.REC0 = REC0 = REC0X[..., p_w:RX]                # [c1 | c2 | h0] per step (view)
+        # per-utterance speaker terms, refilled per run: LSTM1's input row s (W1_s1 + W1_s2) + b
+        # and the transition agent's bias s w_s + b_u
+        pl.XB1 = XB1 = torch.empty(B, 4 * Dd, **f32) if Sd else None
+        W1x = W1[:A + M1 + M2 + Dd]
         C0 = torch.zeros(2, B, A, **f32)
         H0RAW = torch.empty(B, A, **f32)
         L1 = [torch.zeros(2, B, Dd, **f32), torch.zeros(2, B, Dd, **f32)]   # c, h ping-pong
@@ -305,6 +317,7 @@ class FreeRunningDecoder:
         # run) and, with cumulative weights, S1 as the running sum beside a scratch softmax row
         agent = bool(att1_fwd and d.transition_agent)
         cum = bool(att1_fwd and d.cumulative_weights)
+        pl.AB = AB = torch.empty(B, 1, **f32) if agent and Sd else None
         pl.U1 = U1 = torch.empty(Tm + 1, B, **f32) if agent or cum else None
         SMX1 = torch.empty(B, N, **f32) if cum else None
         tf_ = f"{a1}/transition_factor_projection"
@@ -390,18 +403,20 @@ class FreeRunningDecoder:
                 locW=P[f"{a1}/location_layer/kernel"] if att1_fwd else None,
                 v2=P[f"{a2}/attention_v"], e1=E1, e2=E2, part=PART, part_stride=pst,
                 s_out=SMX1 if cum else S1[t + 1], a_out=AL1[t + 1], s2_out=S2[t],
-                ctx=REC0[t + 1], ctx_sb=RX, stats=None, loc_out=None,
+                ctx=REC0[t + 1], ctx_sb=RXW, stats=None, loc_out=None,
                 u_prev=None if U1 is None else U1[t], u_out=U1[t + 1] if agent else None,
                 agent_w=P[f"{tf_}/kernel"] if agent else None,
-                agent_b=P[f"{tf_}/bias"] if agent else None,
+                agent_b=(AB if AB is not None else P[f"{tf_}/bias"]) if agent else None,
+                agent_b_sb=0 if AB is None else 1,
                 state_out=S1[t + 1] if cum else None)
 
         def lstm_stack(t, cur, nxt):
             # LSTM1 on [h0'_t | c1_t c2_t | h1_{t-1}] and LSTM2 on [h1'_t | h2_{t-1}], each one
             # step launch with its whole kernel (input projection included) and bias
-            K.lstm_step_fwd(B=B, U=Dd, K=A + M1 + M2 + Dd, t=t, xproj=None,
-                            bias=P["decoder/lstm1/bias"], rin=H0RAW,
-                            rin1=REC0[t + 1][:, :M1 + M2], rin2=L1[1][cur], W=W1,
+            K.lstm_step_fwd(B=B, U=Dd, K=A + M1 + M2 + Dd, t=t, xproj=XB1,
+                            bias=None if XB1 is not None else P["decoder/lstm1/bias"],
+                            rin=H0RAW,
+                            rin1=REC0[t + 1][:, :M1 + M2], rin2=L1[1][cur], W=W1x,
                             c_prev=L1[0][cur], h_prev=L1[1][cur], mask_c=None, mask_h=None,
                             zc=zc, zh=zh, h_raw=H1RAW, c_out=L1[0][nxt], h_out=L1[1][nxt],
                             gates=GD)
@@ -424,7 +439,7 @@ class FreeRunningDecoder:
                 x = MEL[t - 1][:, M * (r - nf):]
             prenets(x, REC0X[t][:, :p_w])
             # the attention RNN on [prenet | c1 c2 | h0_{t-1}] against its whole kernel
-            K.lstm_step_fwd(B=B, U=A, K=RX, t=t, xproj=None,
+            K.lstm_step_fwd(B=B, U=A, K=RXW, t=t, xproj=None,
                             bias=P["decoder/attention_lstm/bias"], rin=REC0X[t], W=W0,
                             c_prev=C0[cur], h_prev=REC0[t, :, M1 + M2:], mask_c=None,
                             mask_h=None, zc=zc, zh=zh, h_raw=H0RAW, c_out=C0[nxt],
@@ -443,7 +458,7 @@ class FreeRunningDecoder:
         return pl
 
     # ------------------------------------------------------------------ one decode
-    def _prepare(self, pl: _Plan, batch, spk_rows):
+    def _prepare(self, pl: _Plan, batch, spk_rows, spk_dec=None):
         """Per-run inputs into the plan's static buffers: memories, feeds, reset state."""
         m, hp, d = self.m, self.hp, self.d
         P = m.P
@@ -472,6 +487,17 @@ class FreeRunningDecoder:
             ms = "decoder/prenet0"
             K.linear(spk_rows, P[f"{ms}/speaker_projection/kernel"],
                      P[f"{ms}/speaker_projection/bias"], act="softsign", out=pl.sp)
+        if spk_dec is not None:
+            Sd, RX = d.spk_width, d.dec_prenet[-1] + d.m1 + d.m2 + d.att_rnn
+            K.ctx_tail_fill(pl.REC0X, RX, spk_dec, 1, Tm + 1)
+            K.ctx_tail_fill(pl.REC0X, RX + Sd, spk_dec, 1, Tm + 1)
+            ss = pl.REC0X[1, :, RX:]                           # [s | s], just written
+            W1 = P["decoder/lstm1/kernel"]
+            K.linear(ss, W1[d.att_rnn + d.m1 + d.m2 + d.dec:], P["decoder/lstm1/bias"],
+                     out=pl.XB1)
+            if pl.AB is not None:
+                tf_ = "decoder/attention1/transition_factor_projection"
+                K.linear(spk_dec, P[f"{tf_}/kernel"][d.m1 + d.d1:], P[f"{tf_}/bias"], out=pl.AB)
         if pl.XT is not None:                                  # OneHotValidationHelper :103
             M, r, nf = d.num_mels, d.r, hp.n_feed_frame
             tg = batch["mel"].reshape(B, Tm, M * r)
@@ -528,18 +554,25 @@ class FreeRunningDecoder:
         # the encoder BiLSTM as one launch (encoder_lstm.hip) like the training step's
         m1, m2 = encoder_fwd(P, m.bn, hp, d, ids, lengths, None, False, m.ws, sv,
                              persistent=m.persistent_decoder)
-        spk = None
-        if d.multi_speaker:
-            spk = torch.empty(B, d.spk_dim, device=dev)
+        spk = spk_dec = None
+        if d.has_speaker:                       # models/models.py:64-83, the same in every mode
             err = torch.zeros(1, dtype=torch.int32, device=dev)
-            K.embedding_fwd(P["speaker_embedding"], batch["speaker_id"], spk, d.spk_offset, err)
+            s = speaker_vector(P, d, batch.get("speaker_id"), B, dev, err)["s"]
+            spk = s if d.multi_speaker else None
+            spk_dec = s if d.spk_to_decoder else None
+
         def prepare():
             # ---- memories (TF _prepare_memory + memory_layer) into the plan's buffers
-            self._prepare(pl, batch, spk)
+            self._prepare(pl, batch, spk, spk_dec)
             K.seq_mask(m1, pl.lengths, out=pl.V1)
             K.seq_mask(m2, pl.lengths, out=pl.V2)
-            K.linear(pl.V1, P["decoder/attention1/memory_layer/kernel"], out=pl.K1)
-            K.linear(pl.V2, P["decoder/attention2/memory_layer/kernel"], out=pl.K2)
+            Wm1 = P["decoder/attention1/memory_layer/kernel"]
+            Wm2 = P["decoder/attention2/memory_layer/kernel"]
+            K.linear(pl.V1, Wm1[:d.m1], out=pl.K1)
+            K.linear(pl.V2, Wm2[:d.m2], out=pl.K2)
+            if spk_dec is not None:             # the speaker rows of memory_layer, as in training
+                K.rows_bias_fwd(pl.K1, K.linear(spk_dec, Wm1[d.m1:]), pl.lengths)
+                K.rows_bias_fwd(pl.K2, K.linear(spk_dec, Wm2[d.m2:]), pl.lengths)
 
         prepare()
         stop_mode = self.helper == "stop_token"

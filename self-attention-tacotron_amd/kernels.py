@@ -522,6 +522,55 @@ def seq_mask(x: torch.Tensor, lengths: torch.Tensor, out=None):
     return out
 
 
+def rows_bias_fwd(y: torch.Tensor, bias: torch.Tensor, lengths=None, step_major: bool = False):
+    """sat_rows_bias_fwd: y[b, n, :] += bias[b, :] for n < lengths[b] (every row without
+    lengths).  y [B, N, C] (any batch / row strides, unit column stride), or with ``step_major``
+    [T, B, C] (the rows of utterance b are y[:, b])."""
+    _f32(y, "y"); _f32(bias, "bias")
+    if step_major:
+        N, B, C = y.shape
+        sb, sn = y.stride(1), y.stride(0)
+    else:
+        B, N, C = y.shape
+        sb, sn = y.stride(0), y.stride(1)
+    if tuple(bias.shape) != (B, C) or bias.stride(1) != 1 or y.stride(2) != 1:
+        raise ValueError("rows_bias_fwd: bias must be [B, C] beside y, unit column strides")
+    _lib.call("sat_rows_bias_fwd", _p(y), sb, sn, _p(bias), bias.stride(0), B, N, C,
+              _p(lengths), _stream())
+    return y
+
+
+def rows_bias_bwd(dy: torch.Tensor, lengths=None, step_major: bool = False, out=None):
+    """sat_rows_bias_bwd: out[b, :] = sum over n < lengths[b] of dy[b, n, :] (no atomics)."""
+    _f32(dy, "dy")
+    if step_major:
+        N, B, C = dy.shape
+        sb, sn = dy.stride(1), dy.stride(0)
+    else:
+        B, N, C = dy.shape
+        sb, sn = dy.stride(0), dy.stride(1)
+    if out is None:
+        out = torch.empty(B, C, device=dy.device, dtype=torch.float32)
+    if tuple(out.shape) != (B, C) or out.stride(1) != 1 or dy.stride(2) != 1:
+        raise ValueError("rows_bias_bwd: out must be [B, C] beside dy, unit column strides")
+    _lib.call("sat_rows_bias_bwd", _p(dy), sb, sn, _p(out), out.stride(0), B, N, C,
+              _p(lengths), _stream())
+    return out
+
+
+def ctx_tail_fill(ctx: torch.Tensor, col0: int, s: torch.Tensor, t0: int, t1: int):
+    """sat_ctx_tail_fill: ctx[t, b, col0:col0 + S] = s[b] for t0 <= t < t1 (ctx [T, B, W])."""
+    _f32(ctx, "ctx"); _f32(s, "s")
+    T, B, W = ctx.shape
+    S = s.shape[1]
+    if s.shape[0] != B or not 0 <= t0 <= t1 <= T or col0 + S > W or ctx.stride(2) != 1 or \
+            s.stride(1) != 1:
+        raise ValueError("ctx_tail_fill: s [B, S] must fit rows t0..t1 of ctx [T, B, W] at col0")
+    _lib.call("sat_ctx_tail_fill", _p(ctx), ctx.stride(0), ctx.stride(1), col0, _p(s),
+              s.stride(0), t0, t1, B, S, _stream())
+    return ctx
+
+
 def _rs(t) -> int:
     """row stride (elements) of a 2-D view"""
     return 0 if t is None else t.stride(0)

@@ -304,6 +304,25 @@ class Saved(dict):
     pass
 
 
+def speaker_vector(P, d: PR.Dims, speaker_id: Optional[torch.Tensor], B: int, device,
+                   err: torch.Tensor) -> dict:
+    """The speaker vector s [B, S] every destination reads (models/models.py:64-75):
+    speaker_embedding(id), with speaker_for_synthesis in place of the batch's ids when set (in
+    every mode, as the reference), then the ReLU projection when it is on.  Returns the record
+    the backward needs: s, the raw embedding rows, the ids used."""
+    if d.spk_fixed > -1:
+        ids = torch.full((B,), d.spk_fixed, dtype=torch.int64, device=device)
+    else:
+        ids = speaker_id
+    raw = torch.empty(B, d.spk_dim, device=device)
+    K.embedding_fwd(P["speaker_embedding"], ids, raw, d.spk_offset, err)
+    s = raw
+    if d.spk_proj > -1:
+        s = K.linear(raw, P["speaker_embedding_projection/kernel"],
+                     P["speaker_embedding_projection/bias"], act="relu")
+    return dict(s=s, raw=raw, ids=ids)
+
+
 def model_forward(P, bn: BNState, hp, d: PR.Dims, batch: Dict[str, torch.Tensor],
                   masks: Optional[Dict[str, torch.Tensor]], training: bool, ws: K.Workspace,
                   compute_grad_seeds: bool = True, attn_tile: int = 32, pipe=None,
@@ -330,22 +349,24 @@ def model_forward(P, bn: BNState, hp, d: PR.Dims, batch: Dict[str, torch.Tensor]
     dec_in = dec_box[0]
     if aux is not None:
         torch.cuda.current_stream().wait_stream(aux)
-    spk = None
-    if d.multi_speaker:                                               # models/models.py:43-46,69
-        ids_s = batch["speaker_id"]
-        spk = torch.empty(ids_s.shape[0], d.spk_dim, device=m1.device)
+    spk = spk_dec = rec = None
+    if d.has_speaker:                                                 # models/models.py:43-46,64-83
         if health is None:
             sv["spk_err"] = K.zeros(1, dtype=torch.int32, device=m1.device)
         else:
             sv["spk_err"] = K.fill_(health[9:10])
-        K.embedding_fwd(P["speaker_embedding"], ids_s, spk, d.spk_offset, sv["spk_err"])
+        rec = speaker_vector(P, d, batch.get("speaker_id"), ids.shape[0], m1.device,
+                             sv["spk_err"])
+        spk = rec["s"] if d.multi_speaker else None
+        spk_dec = rec["s"] if d.spk_to_decoder else None
     dout, dsv = decoder_forward(P, hp, d, m1, m2, lengths, batch["mel"], masks,
-                                attn_tile=attn_tile, spk=spk, persistent=persistent,
+                                attn_tile=attn_tile, spk=spk, spk_dec=spk_dec,
+                                persistent=persistent,
                                 scratch=scratch, keep_tanh=compute_grad_seeds, inputs=dec_in,
                                 **({} if pipe is None else {"pipe": pipe}))
     sv["dec"] = dsv
-    if spk is not None:
-        dsv.tensors["ms_prenet"]["ids"] = batch["speaker_id"]
+    if rec is not None:
+        dsv.tensors["speaker"] = rec
     mel_r, stop = head_fwd(P, hp, d, dout, masks, sv)
     B, Tp, _ = mel_r.shape
     mel = mel_r.view(B, Tp * d.r, d.num_mels)                         # module.py:1561

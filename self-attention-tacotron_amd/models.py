@@ -260,7 +260,7 @@ class DualSourceSelfAttentionTacotronModel:
         picked = C.load_warm_start(path, sl, ws.vars_to_warm_start)
         for name, a in picked.items():
             self.engine.P[name].copy_(torch.from_numpy(
-                np.ascontiguousarray(PR.to_internal(name, a))))
+                np.ascontiguousarray(self.engine.layout.to_internal(name, a))))
 
     def restore(self, path) -> None:
         """Load ``path`` into the existing arenas (addresses unchanged, captured steps stay
@@ -344,10 +344,11 @@ class DualSourceSelfAttentionTacotronModel:
         arrays = {"source": features.source, "source_length": features.source_length,
                   "mel": codes, "mel_mask": cmask, "done": labels.done,
                   "done_mask": labels.binary_loss_mask, "target_length": labels.target_length}
-        if self.params.use_speaker_embedding:                 # models/models.py:69-70
-            if getattr(features, "speaker_id", None) is None:
+        if self.params.use_speaker_embedding:                 # models/models.py:64-70
+            if getattr(features, "speaker_id", None) is not None:
+                arrays["speaker_id"] = features.speaker_id
+            elif self.engine.d.spk_fixed < 0:     # speaker_for_synthesis replaces the ids
                 raise ValueError("use_speaker_embedding=True needs features.speaker_id")
-            arrays["speaker_id"] = features.speaker_id
         i64 = ("source", "source_length", "target_length", "speaker_id")
         dtypes = {k: torch.int64 if k in i64 else torch.float32 for k in arrays}
         return self._stager.upload(arrays, dev, dtypes)
@@ -378,9 +379,10 @@ class DualSourceSelfAttentionTacotronModel:
         batch = {"source": _to_device(features.source, dev, torch.int64),
                  "source_length": _to_device(features.source_length, dev, torch.int64)}
         if self.params.use_speaker_embedding:
-            if getattr(features, "speaker_id", None) is None:
+            if getattr(features, "speaker_id", None) is not None:
+                batch["speaker_id"] = _to_device(features.speaker_id, dev, torch.int64)
+            elif self.engine.d.spk_fixed < 0:     # speaker_for_synthesis replaces the ids
                 raise ValueError("use_speaker_embedding=True needs features.speaker_id")
-            batch["speaker_id"] = _to_device(features.speaker_id, dev, torch.int64)
         out = FreeRunningDecoder(self.engine, max_iters=self.params.max_iters).run(batch)
         mel = out["mel"]
         codes = torch.zeros_like(mel)

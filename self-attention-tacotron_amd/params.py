@@ -27,6 +27,9 @@ class ParamSpec:
     shape: Tuple[int, ...]
     init: str = "glorot"      # glorot | zeros | ones | const:<v>
     trainable: bool = True
+    # internal row i of a 2-D kernel holds row row_perm[i] of the shape TF would build (None: the
+    # same order).  Only the kernels speaker_embedd_to_decoder widens carry one (_speaker_rows).
+    row_perm: Optional[Tuple[int, ...]] = None
 
 
 @dataclass(frozen=True)
@@ -68,6 +71,19 @@ class Dims:
     # ForwardAttention options of source 1 (modules/forward_attention.py:56-57; hparams.py:113,116)
     transition_agent: bool = False
     cumulative_weights: bool = False
+    # the fork's speaker options (models/models.py:64-83).  multi_speaker above = the vector
+    # reaches the prenet; spk_to_decoder = it is appended to both memories; spk_proj = width of
+    # the ReLU projection in front of both (-1: none); spk_width = S, the vector's width after
+    # it; spk_fixed = speaker_for_synthesis (-1: the batch's speaker_id)
+    spk_to_decoder: bool = False
+    spk_proj: int = -1
+    spk_width: int = 0
+    spk_fixed: int = -1
+
+    @property
+    def has_speaker(self) -> bool:
+        """the speaker-embedding table exists (either destination is on)"""
+        return self.multi_speaker or self.spk_to_decoder
 
 
 def resolve_dims(hp) -> Dims:
@@ -90,6 +106,32 @@ def resolve_dims(hp) -> Dims:
     if getattr(hp, "use_l2_regularization", False):
         # models/models.py:164-171 (ext l2_regularization_loss with a name blacklist)
         raise NotImplementedError("use_l2_regularization=True is not built (off in the configs)")
+    if getattr(hp, "speaker_embedd_to_postnet", False):
+        raise NotImplementedError("speaker_embedd_to_postnet=True: this model builds no postnet")
+    use_spk = bool(hp.use_speaker_embedding)
+    to_dec = bool(getattr(hp, "speaker_embedd_to_decoder", False))
+    proj = int(getattr(hp, "speaker_embedding_projection_out_dim", -1))
+    fixed = int(getattr(hp, "speaker_for_synthesis", -1))
+    if not use_spk and (to_dec or proj > -1 or fixed > -1):
+        # the reference fails here too: it concatenates / projects / looks up a speaker vector
+        # that was never made (models/models.py:64-83)
+        raise ValueError("speaker_embedd_to_decoder / speaker_embedding_projection_out_dim / "
+                         "speaker_for_synthesis need use_speaker_embedding=True")
+    if proj == 0 or proj < -1:
+        raise ValueError(f"speaker_embedding_projection_out_dim={proj}: -1 (off) or a width >= 1")
+    if fixed > -1 and not 0 <= fixed - hp.speaker_embedding_offset < hp.num_speakers:
+        lo = hp.speaker_embedding_offset
+        raise ValueError(f"speaker_for_synthesis={fixed} is outside the speaker table: valid ids "
+                         f"are {lo}..{lo + hp.num_speakers - 1} (speaker_embedding_offset={lo}, "
+                         f"num_speakers={hp.num_speakers})")
+    to_pre = bool(use_spk and hp.speaker_embedd_to_prenet)
+    has_spk = to_pre or (use_spk and to_dec)
+    if not has_spk:
+        proj = -1
+    width = (proj if proj > -1 else hp.speaker_embedding_dim) if has_spk else 0
+    if to_dec and width % 4:
+        raise ValueError(f"speaker_embedd_to_decoder needs a speaker vector width that is a "
+                         f"multiple of 4 (16-byte rows), got {width}")
     half = hp.cbhg_out_units // 2
     assert hp.cbhg_out_units % 2 == 0
     if hp.projection2_out_channels != hp.encoder_prenet_out_units[-1]:
@@ -113,7 +155,7 @@ def resolve_dims(hp) -> Dims:
         dec=hp.decoder_out_units, dsa=hp.decoder_self_attention_out_units,
         dec_heads=hp.decoder_self_attention_num_heads, dec_hops=hp.decoder_self_attention_num_hop,
         num_mels=hp.num_mels, r=hp.outputs_per_step,
-        multi_speaker=bool(hp.use_speaker_embedding and hp.speaker_embedd_to_prenet),
+        multi_speaker=to_pre,
         num_speakers=hp.num_speakers, spk_dim=hp.speaker_embedding_dim,
         spk_offset=hp.speaker_embedding_offset,
         # only ForwardAttention reads the two options (BahdanauAttention ignores them,
@@ -121,20 +163,33 @@ def resolve_dims(hp) -> Dims:
         transition_agent=bool(hp.use_forward_attention_transition_agent
                               and hp.attention == "forward"),
         cumulative_weights=bool(hp.cumulative_weights and hp.attention == "forward"),
+        spk_to_decoder=bool(use_spk and to_dec), spk_proj=proj, spk_width=width,
+        spk_fixed=fixed if has_spk else -1,
     )
 
 
+def _speaker_rows(blocks, tails) -> Tuple[int, ...]:
+    """Row permutation of a kernel whose TF rows are the given consecutive blocks, the speaker
+    blocks (indices ``tails``) moved behind the others: the kernels keep reading contiguous
+    [c1 | c2] rows and the speaker rows form one trailing block."""
+    starts = np.concatenate([[0], np.cumsum(blocks)])
+    order = [i for i in range(len(blocks)) if i not in tails] + list(tails)
+    return tuple(int(r) for i in order for r in range(starts[i], starts[i + 1]))
+
+
 def _dense(out: List[ParamSpec], scope: str, fan_in: int, fan_out: int, bias: bool = True,
-           bias_init: str = "zeros") -> None:
-    out.append(ParamSpec(f"{scope}/kernel", (fan_in, fan_out)))
+           bias_init: str = "zeros", row_perm=None) -> None:
+    out.append(ParamSpec(f"{scope}/kernel", (fan_in, fan_out), row_perm=row_perm))
     if bias:
         out.append(ParamSpec(f"{scope}/bias", (fan_out,), bias_init))
 
 
 def _attention(out: List[ParamSpec], scope: str, kind: str, mem: int, query: int, units: int,
-               loc_k: int, loc_f: int, transition_agent: bool = False) -> None:
+               loc_k: int, loc_f: int, transition_agent: bool = False, spk: int = 0) -> None:
+    """``spk`` = S when the speaker vector is appended to the memory (its rows follow the
+    memory's in memory_layer: no permutation)."""
     # BahdanauAttention memory/query layers: Dense(num_units, use_bias=False)
-    _dense(out, f"{scope}/memory_layer", mem, units, bias=False)
+    _dense(out, f"{scope}/memory_layer", mem + spk, units, bias=False)
     _dense(out, f"{scope}/query_layer", query, units, bias=False)
     if kind == "forward":
         # modules/forward_attention.py:16-23 (v_a xavier, b_a zeros), :68-78 (conv + location layer)
@@ -145,7 +200,9 @@ def _attention(out: List[ParamSpec], scope: str, kind: str, mem: int, query: int
         _dense(out, f"{scope}/location_layer", loc_f, units, bias=False)
         if transition_agent:
             # :80-86 Dense(1, use_bias=True, sigmoid) over [context | processed_query] (:113)
-            _dense(out, f"{scope}/transition_factor_projection", mem + units, 1)
+            # with the speaker rows: TF order [c1 | s | pq], kept as [c1 | pq | s]
+            _dense(out, f"{scope}/transition_factor_projection", mem + spk + units, 1,
+                   row_perm=_speaker_rows((mem, spk, units), (1,)) if spk else None)
     else:
         # TF _bahdanau_score: attention_v [num_units], no bias (normalize=False)
         out.append(ParamSpec(f"{scope}/attention_v", (units,)))
@@ -200,11 +257,14 @@ def param_specs(hp) -> List[ParamSpec]:
         _mha(s, f"encoder/self_attention{h}/mha", d.m2, d.m2)
         _dense(s, f"encoder/self_attention{h}/transform", d.m2, d.m2)
     # DualSourceTransformerDecoder (modules/module.py:1455-1562)
-    if d.multi_speaker:
+    if d.has_speaker:
         s.append(ParamSpec("speaker_embedding", (d.num_speakers, d.spk_dim)))
+        if d.spk_proj > -1:                                           # models/models.py:72-75
+            _dense(s, "speaker_embedding_projection", d.spk_dim, d.spk_proj)
+    if d.multi_speaker:
         p0 = d.dec_prenet[0]                                          # multi_speaker_modules.py:19-21
         _dense(s, "decoder/prenet0/dense0", d.feed, p0)
-        _dense(s, "decoder/prenet0/speaker_projection", d.spk_dim, p0)
+        _dense(s, "decoder/prenet0/speaker_projection", d.spk_width, p0)
         _dense(s, "decoder/prenet0/dense", p0, p0)
         w = p0
         for i, u in enumerate(d.dec_prenet[1:], start=1):
@@ -216,11 +276,16 @@ def param_specs(hp) -> List[ParamSpec]:
             _dense(s, f"decoder/prenet{i}", w, u)
             w = u
     p_last = w
-    _dense(s, "decoder/attention_lstm", p_last + d.m1 + d.m2 + d.att_rnn, 4 * d.att_rnn)
+    # speaker_embedd_to_decoder (models/models.py:77-83): both memories, hence both contexts,
+    # grow by S columns -- TF rows [.. | c1 | s | c2 | s | ..], kept as [.. | c1 | c2 | .. | s | s]
+    S = d.spk_width if d.spk_to_decoder else 0
+    _dense(s, "decoder/attention_lstm", p_last + d.m1 + d.m2 + 2 * S + d.att_rnn, 4 * d.att_rnn,
+           row_perm=_speaker_rows((p_last, d.m1, S, d.m2, S, d.att_rnn), (2, 4)) if S else None)
     _attention(s, "decoder/attention1", d.att1, d.m1, d.att_rnn, d.d1, d.loc_k, d.loc_f,
-               transition_agent=d.transition_agent)
-    _attention(s, "decoder/attention2", d.att2, d.m2, d.att_rnn, d.d2, d.loc_k, d.loc_f)
-    _dense(s, "decoder/lstm1", d.att_rnn + d.m1 + d.m2 + d.dec, 4 * d.dec)
+               transition_agent=d.transition_agent, spk=S)
+    _attention(s, "decoder/attention2", d.att2, d.m2, d.att_rnn, d.d2, d.loc_k, d.loc_f, spk=S)
+    _dense(s, "decoder/lstm1", d.att_rnn + d.m1 + d.m2 + 2 * S + d.dec, 4 * d.dec,
+           row_perm=_speaker_rows((d.att_rnn, d.m1, S, d.m2, S, d.dec), (2, 4)) if S else None)
     _dense(s, "decoder/lstm2", d.dec + d.dec, 4 * d.dec)
     for h in range(d.dec_hops):                                       # module.py:700-709
         _mha(s, f"decoder/self_attention{h}/mha", d.dec, d.dsa)
@@ -290,9 +355,12 @@ def is_lstm_param(name: str) -> bool:
     return any(name == f"{s}/kernel" or name == f"{s}/bias" for s in LSTM_SCOPES)
 
 
-def to_internal(name: str, a: np.ndarray) -> np.ndarray:
+def to_internal(name: str, a: np.ndarray, row_perm=None) -> np.ndarray:
     """TF LSTMCell column order [i(U) j(U) f(U) o(U)] -> gate-interleaved [U][4] (the layout the
-    HIP step kernels read: one float4 per unit).  Other parameters are unchanged."""
+    HIP step kernels read: one float4 per unit).  ``row_perm`` (ParamSpec.row_perm): the rows
+    are reordered first.  Other parameters are unchanged."""
+    if row_perm is not None:
+        a = a[np.asarray(row_perm)]
     if not is_lstm_param(name):
         return a
     if a.ndim == 2:
@@ -301,13 +369,18 @@ def to_internal(name: str, a: np.ndarray) -> np.ndarray:
     return a.reshape(4, -1).T.reshape(-1)
 
 
-def from_internal(name: str, a: np.ndarray) -> np.ndarray:
-    if not is_lstm_param(name):
-        return a
-    if a.ndim == 2:
-        K, G = a.shape
-        return a.reshape(K, G // 4, 4).transpose(0, 2, 1).reshape(K, G)
-    return a.reshape(-1, 4).T.reshape(-1)
+def from_internal(name: str, a: np.ndarray, row_perm=None) -> np.ndarray:
+    if is_lstm_param(name):
+        if a.ndim == 2:
+            K, G = a.shape
+            a = a.reshape(K, G // 4, 4).transpose(0, 2, 1).reshape(K, G)
+        else:
+            a = a.reshape(-1, 4).T.reshape(-1)
+    if row_perm is not None:
+        out = np.empty_like(a)
+        out[np.asarray(row_perm)] = a
+        a = out
+    return a
 
 
 class Layout:
@@ -317,6 +390,7 @@ class Layout:
         self.specs = list(specs)
         self.offsets: Dict[str, int] = {}
         self.shapes: Dict[str, Tuple[int, ...]] = {}
+        self.row_perms = {p.name: p.row_perm for p in self.specs if p.row_perm is not None}
         off = 0
         for p in self.specs:
             off = (off + ALIGN_FLOATS - 1) // ALIGN_FLOATS * ALIGN_FLOATS
@@ -333,7 +407,7 @@ class Layout:
             o = self.offsets[p.name]
             a = np.asarray(values[p.name], np.float32).reshape(p.shape)
             if internal:
-                a = to_internal(p.name, a)
+                a = to_internal(p.name, a, p.row_perm)
             flat[o:o + int(np.prod(p.shape))] = a.ravel()
         return flat
 
@@ -343,8 +417,15 @@ class Layout:
         for p in self.specs:
             o = self.offsets[p.name]
             a = np.asarray(flat[o:o + int(np.prod(p.shape))]).reshape(p.shape)
-            out[p.name] = from_internal(p.name, a) if internal else a
+            out[p.name] = from_internal(p.name, a, p.row_perm) if internal else a
         return out
+
+    def to_internal(self, name: str, a: np.ndarray) -> np.ndarray:
+        """TF-layout array of parameter ``name`` -> the arena's layout (rows and LSTM columns)."""
+        return to_internal(name, a, self.row_perms.get(name))
+
+    def from_internal(self, name: str, a: np.ndarray) -> np.ndarray:
+        return from_internal(name, a, self.row_perms.get(name))
 
     def views(self, arena) -> Dict[str, "object"]:
         """Name -> view into a torch (or numpy) 1-D arena."""
