@@ -401,6 +401,8 @@ extern "C" int sat_encoder_lstm_fwd(const SatEncLstmFwd* a, void* stream) {
   SAT_CHECK_ARG(aligned16(a->G_fw) && aligned16(a->G_bw) && aligned16(a->W_fw) && aligned16(a->W_bw) &&
                 aligned16(a->X_fw) && aligned16(a->X_bw) && a->x_sb % 4 == 0 && a->x_sn % 4 == 0,
                 "sat_encoder_lstm_fwd: 16-byte aligned operands");
+  SAT_CHECK_ARG(aligned16(a->mc_fw) && aligned16(a->mh_fw) && aligned16(a->mc_bw) && aligned16(a->mh_bw),
+                "sat_encoder_lstm_fwd: 16-byte aligned zoneout masks");
   EncFwdP p;
   p.B = a->B; p.N = a->N; p.zc = a->zc; p.zh = a->zh;
   p.X[0] = a->X_fw; p.X[1] = a->X_bw; p.x_sb = a->x_sb; p.x_sn = a->x_sn;
@@ -426,6 +428,11 @@ extern "C" int sat_encoder_lstm_bwd(const SatEncLstmBwd* a, void* stream) {
   SAT_CHECK_ARG(aligned16(a->W_fw) && aligned16(a->W_bw) && aligned16(a->G_fw) && aligned16(a->G_bw) &&
                 aligned16(a->DG_fw) && aligned16(a->DG_bw),
                 "sat_encoder_lstm_bwd: 16-byte aligned operands");
+  // the BPTT streams these into LDS 16 bytes per lane (LDS-DMA)
+  SAT_CHECK_ARG(aligned16(a->DY) && a->dy_sb % 4 == 0 && a->dy_sn % 4 == 0 && aligned16(a->CS_fw) &&
+                aligned16(a->CS_bw) && aligned16(a->mc_fw) && aligned16(a->mh_fw) &&
+                aligned16(a->mc_bw) && aligned16(a->mh_bw),
+                "sat_encoder_lstm_bwd: DY, CS and the zoneout masks must be 16-byte aligned, DY strides % 4");
   EncBwdP p;
   p.B = a->B; p.N = a->N; p.zc = a->zc; p.zh = a->zh;
   p.W[0] = a->W_fw; p.W[1] = a->W_bw; p.G[0] = a->G_fw; p.G[1] = a->G_bw;

@@ -400,12 +400,19 @@ using namespace sat;
 static int check_fwd(const SatLstmFwd* a, LstmFwdP& p, size_t& shm) {
   SAT_CHECK_ARG(a && a->B > 0 && a->U > 0 && a->K >= 0, "sat_lstm_step_fwd: bad sizes");
   SAT_CHECK_ARG(a->K % 4 == 0 && a->rin_sb % 4 == 0, "sat_lstm_step_fwd: K and rin stride must be multiples of 4");
-  SAT_CHECK_ARG((a->K == 0 || a->rin) && a->W && a->c_out && a->h_out, "sat_lstm_step_fwd: null pointer");
+  SAT_CHECK_ARG(a->W && a->c_out && a->h_out, "sat_lstm_step_fwd: null pointer");
+  // 16-byte loads: one float4 per (row, unit) of xproj / bias / gates, per (k, unit) of W, per
+  // four columns of the input rows
+  SAT_CHECK_ARG(aligned16(a->xproj) && (!a->xproj || a->xproj_sb % 4 == 0) && aligned16(a->bias) &&
+                aligned16(a->gates) && aligned16(a->W) && aligned16(a->rin),
+                "sat_lstm_step_fwd: xproj, bias, gates, W and rin must be 16-byte aligned, xproj stride % 4");
   SAT_CHECK_ARG((a->mask_c == nullptr) == (a->mask_h == nullptr), "sat_lstm_step_fwd: masks come in pairs");
   SAT_CHECK_ARG(a->K1 >= 0 && a->K2 >= 0 && a->K1 % 4 == 0 && a->K2 % 4 == 0 &&
                 a->K1 + a->K2 <= a->K && (a->K1 == 0 || (a->rin1 && a->rin1_sb % 4 == 0 && aligned16(a->rin1))) &&
                 (a->K2 == 0 || (a->rin2 && a->rin2_sb % 4 == 0 && aligned16(a->rin2))),
                 "sat_lstm_step_fwd: input segments need K1, K2, strides % 4 and 16-byte alignment");
+  // rin may be NULL when the further segments cover the whole row (it is never read then)
+  SAT_CHECK_ARG(a->K1 + a->K2 == a->K || a->rin, "sat_lstm_step_fwd: null pointer");
   p.B = a->B; p.U = a->U; p.K = a->K;
   p.xproj = a->xproj; p.xproj_sb = a->xproj_sb; p.bias = a->bias;
   p.rin = a->rin; p.rin_sb = a->rin_sb; p.W = a->W;
@@ -458,6 +465,8 @@ static int check_bwd(const SatLstmBwd* a, LstmBwdP& p, size_t& shm) {
   SAT_CHECK_ARG(a && a->B > 0 && a->U > 0, "sat_lstm_step_bwd: bad sizes");
   SAT_CHECK_ARG(a->W && a->gates && a->dgates && a->dh_carry_out && a->dc_carry_out,
                 "sat_lstm_step_bwd: null pointer");
+  SAT_CHECK_ARG(aligned16(a->gates) && aligned16(a->dgates),
+                "sat_lstm_step_bwd: gates and dgates must be 16-byte aligned");
   SAT_CHECK_ARG(a->hoff >= 0 && a->hoff + a->U <= a->K, "sat_lstm_step_bwd: hoff out of range");
   SAT_CHECK_ARG((a->dq0 ? a->dq0_n : 0) + (a->dq1 ? a->dq1_n : 0) <= kMaxDq,
                 "sat_lstm_step_bwd: query width > 320");
