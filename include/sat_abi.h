@@ -444,6 +444,12 @@ int sat_lstm_steps_bwd(const SatLstmBwd* steps, int32_t n, void* stream);
  * Outputs: s_out (softmax alignments = next location-conv input), a_out (alpha = returned
  * alignments), s2_out, contexts [c1 | c2] into ctx (row stride ctx_sb), stats [B][4] for the
  * backward.  e1/e2/part are scratch.
+ * Refused with SAT_ERR_ARGUMENT before anything is launched: K1, V1, K2, V2 or part not 16-byte
+ * aligned, part_stride % 4 != 0 (the tile kernels read the key / value rows and write the partial
+ * contexts as float4); D1, D2, M1 or M2 < 1; D1 % 32 != 0 or > 256, D2 not 32 or 64, M1 % 4 != 0
+ * or > 256, M2 % 4 != 0 or > 32; N > 512 (16 tiles of NT = 32 positions); att1_forward with F < 1,
+ * F > 8, KW < 1 or KW > 32 (forward attention without location features is not a step the
+ * backward has).
  * The two ForwardAttention options (modules/forward_attention.py:80-86, 111-121) are the trailing
  * fields; all of them NULL (a zero-initialised struct) is the plain step above:
  *   u_prev   [B] transition factor u_{t-1} per utterance, used instead of the scalar u;
@@ -503,6 +509,9 @@ int sat_attn_step_fwd(const SatAttnStep* args, void* stream);
  * the energy gradients of step t (history rows for sat_attn_param_grads).  Only the critical
  * path runs per step: parameter gradients are one pass after the loop (sat_attn_param_grads),
  * the value gradients dV = alignments^T dctx one batched GEMM.
+ * Refused with SAT_ERR_ARGUMENT: D1, D2, M1 or M2 < 1, N > 1024, NT not 8, 16 or 32, and
+ * att1_forward with F < 1, F > 8, KW < 1 or KW > 32 (with F = 0 the kernel would back-propagate an
+ * additive step, which is not what sat_attn_step_fwd ran).
  * Transition agent / cumulative weights (trailing fields; all zero = the plain step):
  *   u_prev  [B] the u_{t-1} the forward step used, instead of the scalar u;
  *   u_t     [B] the u_t step t+1 used: dalpha_t[n] = (1-u_t) Y[n] + u_t Y[n+1] is that step's

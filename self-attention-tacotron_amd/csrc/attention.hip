@@ -612,14 +612,30 @@ extern "C" int sat_attn_step_fwd(const SatAttnStep* a, void* stream) {
   SAT_CHECK_ARG(a && a->B > 0 && a->N > 0, "sat_attn_step_fwd: bad sizes");
   SAT_CHECK_ARG(a->D1 <= kMaxD && a->D2 <= kMaxD && a->M2 >= 0, "sat_attn_step_fwd: D > 256");
   SAT_CHECK_ARG(a->NT == kNT, "sat_attn_step_fwd: tile size must be 32");
-  SAT_CHECK_ARG(a->N <= 1024 && a->M1 <= 256 && a->M1 % 4 == 0 && a->M2 <= 32 && a->M2 % 4 == 0,
-                "sat_attn_step_fwd: N <= 1024, M1 <= 256, M2 <= 32 (multiples of 4)");
+  // the kernels clamp their float4 loads with min(idx, D / 4 - 1): a zero dimension would index -1
+  SAT_CHECK_ARG(a->D1 >= 1 && a->D2 >= 1 && a->M1 >= 1 && a->M2 >= 1,
+                "sat_attn_step_fwd: D1, D2, M1, M2 must be >= 1");
+  // 16 tiles of 32 positions is what the combine kernel's header reduction holds
+  SAT_CHECK_ARG(a->N <= 16 * kNT, "sat_attn_step_fwd: N <= 512 (16 tiles of 32 positions)");
+  SAT_CHECK_ARG(a->M1 <= 256 && a->M1 % 4 == 0 && a->M2 <= 32 && a->M2 % 4 == 0,
+                "sat_attn_step_fwd: M1 <= 256, M2 <= 32 (multiples of 4)");
   SAT_CHECK_ARG(a->D1 % 32 == 0 && a->D1 <= 256 && a->D2 % 32 == 0 && a->D2 <= 64,
                 "sat_attn_step_fwd: D1 % 32 == 0 (<= 256), D2 in {32, 64}");
+  // att1_forward with F = 0 would run the forward recursion without location features here while
+  // the backward (FWD = F > 0) back-propagates a plain additive step; F < 0 and KW < 1 index the
+  // location-conv LDS below its start
+  SAT_CHECK_ARG(!a->att1_forward || (a->F >= 1 && a->KW >= 1),
+                "sat_attn_step_fwd: forward attention needs F >= 1 and KW >= 1");
   SAT_CHECK_ARG(!a->att1_forward || a->F <= 8, "sat_attn_step_fwd: F <= 8");
   SAT_CHECK_ARG(!a->att1_forward || (a->F <= kMaxF && a->KW <= kMaxKW && a->F * a->D1 <= kMaxF * kMaxD),
                 "sat_attn_step_fwd: location conv too large");
   SAT_CHECK_ARG(a->part_stride >= sat_attn_part_stride(a->M1, a->M2), "sat_attn_step_fwd: part stride");
+  // the tile kernels read the key / value rows and write the partial contexts (part + 8,
+  // part + 8 + M1) as float4; D1 % 32, D2 % 32, M1 % 4 and M2 % 4 keep every row on 16 bytes
+  SAT_CHECK_ARG(a->part_stride % 4 == 0, "sat_attn_step_fwd: part_stride must be a multiple of 4");
+  SAT_CHECK_ARG(aligned16(a->K1) && aligned16(a->V1) && aligned16(a->K2) && aligned16(a->V2) &&
+                aligned16(a->part),
+                "sat_attn_step_fwd: K1, V1, K2, V2 and part must be 16-byte aligned");
   SAT_CHECK_ARG(a->ntiles <= 16 && a->ntiles == ceil_div(a->N, a->NT), "sat_attn_step_fwd: ntiles must be <= 16");
   SAT_CHECK_ARG(a->D2 <= 64, "sat_attn_step_fwd: D2 <= 64");
   SAT_CHECK_ARG(a->q && a->K1 && a->V1 && a->K2 && a->V2 && a->lengths && a->v1 && a->v2 &&
@@ -1350,6 +1366,10 @@ extern "C" int sat_attn_step_bwd(const SatAttnStepBwd* a, void* stream) {
                 "sat_attn_step_bwd: M1 <= 256");
   SAT_CHECK_ARG((a->NT == 8 || a->NT == 16 || a->NT == 32) && a->ntiles == ceil_div(a->N, a->NT),
                 "sat_attn_step_bwd: tile size must be 8, 16 or 32");
+  // F = 0 with att1_forward would be back-propagated as an additive step (FWD = F > 0), which is
+  // not what the forward ran; F < 0 would dispatch the F = 8 kernel on smaller operands
+  SAT_CHECK_ARG(!a->att1_forward || (a->F >= 1 && a->KW >= 1),
+                "sat_attn_step_bwd: forward attention needs F >= 1 and KW >= 1");
   SAT_CHECK_ARG(!a->att1_forward || (a->F <= kMaxFb && a->KW <= kMaxKW),
                 "sat_attn_step_bwd: location conv too large (F <= 8)");
   SAT_CHECK_ARG(a->dctx && a->ctx_t && a->V1 && a->V2 && a->s_t && a->a_t && a->s2_t && a->q &&
