@@ -42,8 +42,8 @@ extern "C" {
  * wgrad_stream / wgrad_ws (deferred weight gradients: sat_mha_bwd_wgrad); 9: the transition agent
  * and cumulative weights of ForwardAttention (trailing fields of SatAttnStep / SatAttnStepBwd,
  * sat_attn_agent_bwd); 10: SatAttnStep.agent_b_sb, the speaker-vector kernels (sat_rows_bias_fwd /
- * _bwd, sat_ctx_tail_fill). */
-#define SAT_ABI_VERSION 10
+ * _bwd, sat_ctx_tail_fill); 11: the summary image kernels (sat_image_minmax / sat_image_render). */
+#define SAT_ABI_VERSION 11
 
 /* ---------------------------------------------------------------- library */
 int sat_version(void);                         /* 100*major + minor */
@@ -963,6 +963,33 @@ int sat_exchange_unpack(const float* tail, int32_t n_health, int32_t* health, vo
  * n_words == 0 is a no-op. */
 int sat_arena_digest(const void* buf, int64_t n_words, int64_t base_index,
                      int32_t count_nonfinite, uint64_t* out, void* stream);
+
+/* ---------------------------------------------------------------- training summaries
+ * 8-bit grayscale images of the plotted tensors (the reference's MetricsSaver alignment plots,
+ * models/models.py:191-199, 238-247; sat_amd/summary.py writes them as PNG image summaries).
+ * Element (r, c) of image i is src[base[i] + c * col_stride + r]: the image's row axis is the
+ * source's contiguous axis (alignment history A[t][b][n]: rows n, columns t, col_stride B*N;
+ * self-attention P[b][h][q][k]: rows k, columns q; mel X[b][t][m]: rows m, columns t).  Image i
+ * is the crop rows[i] x cols[i] (device int32 arrays, clamped to the canvas in the kernels; reads
+ * outside src[0, src_n) give 0).  rows_host / cols_host (nullable) are host copies of the two
+ * arrays for callers that have them: then rows[i] > Rmax or cols[i] > Cmax is refused here.
+ *   sat_image_minmax: minmax[2i], minmax[2i+1] = min, max over the FINITE pixels of crop i
+ *     (0, 0 when there is none), nonfinite[i] = the number of NaN / inf pixels.
+ *   sat_image_render: canvas[i][line][c] (uint8 [n_images][Rmax][Cmax]) =
+ *     q(src(r, c)) with line = rows[i] - 1 - r (source row 0 is the crop's bottom line, as an
+ *     origin='lower' plot), q(x) = clamp(floor(255 * (x - lo) / (hi - lo) + 0.5), 0, 255) in
+ *     fp32 with every operation rounded separately, 0 where hi == lo or x is not finite; every
+ *     canvas pixel outside the crop is 0.  One launch covers all n_images (<= 65535).
+ * Refused with SAT_ERR_ARGUMENT before anything is launched: a null pointer, a negative size,
+ * src not 4-byte aligned, and crops larger than the canvas where the host copies are given. */
+int sat_image_minmax(const float* src, int64_t src_n, const int64_t* base, const int32_t* rows,
+                     const int32_t* cols, int64_t col_stride, int32_t n_images, int32_t Rmax,
+                     int32_t Cmax, const int32_t* rows_host, const int32_t* cols_host,
+                     float* minmax, int32_t* nonfinite, void* stream);
+int sat_image_render(const float* src, int64_t src_n, const int64_t* base, const int32_t* rows,
+                     const int32_t* cols, int64_t col_stride, int32_t n_images, int32_t Rmax,
+                     int32_t Cmax, const int32_t* rows_host, const int32_t* cols_host,
+                     const float* minmax, uint8_t* canvas, void* stream);
 
 /* ---------------------------------------------------------------- dataset records (host)
  * TFRecord framing of the dataset path: datasets/ljspeech/dataset.py:96-112 reads

@@ -273,6 +273,8 @@ SIGNATURES.update({
     "sat_exchange_pack": [_P, _I32, _P, _I64, _P, _F, _P],
     "sat_exchange_unpack": [_P, _I32, _P, _P],
     "sat_arena_digest": [_P, _I64, _I64, _I32, _P, _P],
+    "sat_image_minmax": [_P, _I64, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P],
+    "sat_image_render": [_P, _I64, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P],
 })
 
 RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
@@ -294,7 +296,7 @@ RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
 
 _lib: Optional[ctypes.CDLL] = None
 # include/sat_abi.h SAT_ABI_VERSION this binding's structs follow
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 def load(path: str = LIB_PATH) -> ctypes.CDLL:

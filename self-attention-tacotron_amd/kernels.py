@@ -1048,3 +1048,51 @@ def mha_bwd(d):
 def mha_bwd_wgrad(d):
     """the four projections' weight / bias gradients a weight-deferred mha_bwd left for later"""
     _lib.check(_lib.load().sat_mha_bwd_wgrad(ctypes.byref(d), _stream()), "sat_mha_bwd_wgrad")
+
+
+# ---- training-summary images (csrc/summary.hip; sat_amd/summary.py)
+def _host_i32(v, n):
+    """A host copy of a crop-length array for the entry's own range check (None: not known)."""
+    if v is None:
+        return None, None
+    a = (ctypes.c_int32 * n)(*[int(x) for x in v])
+    return a, ctypes.cast(a, ctypes.c_void_p)
+
+
+def _image_args(src, base, rows, cols, col_stride, Rmax, Cmax, rows_host, cols_host):
+    n = int(base.numel())
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("image source: a contiguous float32 tensor")
+    if base.dtype != torch.int64 or rows.dtype != torch.int32 or cols.dtype != torch.int32:
+        raise ValueError("image crops: base int64, rows / cols int32")
+    if rows.numel() != n or cols.numel() != n:
+        raise ValueError("image crops: base, rows and cols must have one entry per image")
+    for h in (rows_host, cols_host):
+        if h is not None and len(h) != n:
+            raise ValueError("image crops: host copies must have one entry per image")
+    keep_r, pr = _host_i32(rows_host, n)
+    keep_c, pc = _host_i32(cols_host, n)
+    return (keep_r, keep_c), (_p(src), src.numel(), _p(base), _p(rows), _p(cols), int(col_stride),
+                              n, int(Rmax), int(Cmax), pr, pc)
+
+
+def image_minmax(src, base, rows, cols, col_stride, Rmax, Cmax, minmax, nonfinite,
+                 rows_host=None, cols_host=None):
+    """Per-image {min, max} of the finite pixels into ``minmax`` [I, 2] (float32) and the
+    non-finite count into ``nonfinite`` [I] (int32); see include/sat_abi.h."""
+    keep, args = _image_args(src, base, rows, cols, col_stride, Rmax, Cmax, rows_host, cols_host)
+    if minmax.numel() < 2 * args[6] or nonfinite.numel() < args[6]:
+        raise ValueError("image_minmax: outputs too small")
+    _lib.call("sat_image_minmax", *args, _p(minmax), _p(nonfinite), _stream())
+
+
+def image_render(src, base, rows, cols, col_stride, minmax, canvas, rows_host=None,
+                 cols_host=None):
+    """uint8 ``canvas`` [I, Rmax, Cmax] from the crops of ``src`` and their ``minmax``."""
+    I, Rmax, Cmax = canvas.shape
+    if canvas.dtype != torch.uint8 or not canvas.is_contiguous() or I != base.numel():
+        raise ValueError("image_render: canvas must be contiguous uint8 [images, Rmax, Cmax]")
+    keep, args = _image_args(src, base, rows, cols, col_stride, Rmax, Cmax, rows_host, cols_host)
+    if minmax.numel() < 2 * I:
+        raise ValueError("image_render: minmax too small")
+    _lib.call("sat_image_render", *args, _p(minmax), _p(canvas), _stream())

@@ -176,8 +176,15 @@ class DualSourceSelfAttentionTacotronModel:
     def __init__(self, params, model_dir=None, config=None, warm_start_from=None,
                  device="cuda", seed: int = 1234,
                  init_values: Optional[Dict[str, np.ndarray]] = None,
-                 graph_cache: Optional[int] = None, graph_t_quantum: Optional[int] = None):
-        """``graph_cache``: captured training steps kept per padded batch shape (LRU; 0 = every
+                 graph_cache: Optional[int] = None, graph_t_quantum: Optional[int] = None,
+                 summaries: bool = False):
+        """``summaries`` (with a ``model_dir``): TRAIN writes TensorBoard scalars every
+        ``save_summary_steps`` steps and, under ``save_training_time_metrics``, alignment / mel
+        images every ``alignment_save_steps`` steps into ``model_dir``; ``evaluate()`` writes
+        its metrics and images into ``model_dir/eval`` (summary.py).  Off by default: no event
+        file and no extra launch.
+
+        ``graph_cache``: captured training steps kept per padded batch shape (LRU; 0 = every
         TRAIN step eager; default SAT_GRAPH_CACHE or 0); ``graph_t_quantum``: pad T' to a
         multiple of it before the lookup (default SAT_GRAPH_T_QUANTUM or 0 = exact shapes;
         train.StepGraphCache).  Default eager: with the pinned asynchronous upload the eager
@@ -218,6 +225,12 @@ class DualSourceSelfAttentionTacotronModel:
         self._seed_offset = 1000003 * dp.rank()
         self._seed = seed + self._seed_offset
         self._eval_decoder = None
+        # event files: rank 0 alone writes (no other rank queues, launches or communicates)
+        self.summaries = bool(summaries) and bool(model_dir) and dp.rank() == 0
+        self._recorders: Dict[str, object] = {}
+        self._eval_images = False
+        self._step_rate = None
+        self._summary_rehearsed = False
         if newest is not None:
             self.restore(newest)
 
@@ -353,6 +366,160 @@ class DualSourceSelfAttentionTacotronModel:
         dtypes = {k: torch.int64 if k in i64 else torch.float32 for k in arrays}
         return self._stager.upload(arrays, dev, dtypes)
 
+    # ---- summaries (summary.py)
+    def _recorder(self, sub: str = ""):
+        """The event-file recorder of ``model_dir`` (TRAIN) or ``model_dir/eval``."""
+        from . import summary as S
+        r = self._recorders.get(sub)
+        if r is None:
+            logdir = os.path.join(self.model_dir, sub) if sub else self.model_dir
+            r = S.SummaryRecorder(S.EventFileWriter(logdir), self.engine.device)
+            self._recorders[sub] = r
+        return r
+
+    def flush_summaries(self) -> None:
+        """Block until every queued summary is in its event file; raise what the writer met."""
+        for r in self._recorders.values():
+            r.flush()
+
+    def close_summaries(self) -> None:
+        recs, self._recorders = self._recorders, {}
+        for r in recs.values():
+            r.close()
+
+    def _image_groups(self, batch, features, labels, al1, al2, mel, mel_target, enc_probs=(),
+                      dec_probs=()):
+        """The reference's MetricsSaver plots for the first min(B, 3) utterances as
+        summary.ImageGroup lists.  Every stride and canvas size comes from the plotted tensor's
+        own shape (a captured step may have padded T' beyond the caller's batch,
+        StepGraphCache._pad_t); the crops come from the batch's lengths.  ``al1`` / ``al2`` =
+        (tensor, offset of step 0 of utterance 0, utterance stride, step stride, steps) of an
+        alignment history whose memory axis is contiguous; ``mel`` / ``mel_target`` [B, T, M];
+        ``enc_probs`` / ``dec_probs`` [B, H, L, L] softmax probabilities per hop."""
+        from .summary import ImageGroup
+        r = self.params.outputs_per_step
+        B, N = batch["source"].shape
+        k = min(B, 3)
+        T_all = min(mel.shape[1], mel_target.shape[1])
+        src_len = batch["source_length"][:k].to(torch.int32)
+        tgt_len = batch["target_length"][:k].to(torch.int32).clamp(max=T_all)
+        stp_len = ((tgt_len + (r - 1)) // r).clamp(max=min(al1[4], al2[4]))
+        dev = src_len.device
+
+        def host(x, f=lambda v: v):
+            # the host's own copy of the lengths, when it was given one: the kernels' entries
+            # then check the crops against the canvas before launching
+            return [f(int(v)) for v in np.asarray(x)[:k]] if isinstance(x, np.ndarray) else None
+        h_src = host(getattr(features, "source_length", None))
+        h_tgt = host(getattr(labels, "target_length", None), lambda v: min(v, T_all))
+        h_stp = host(getattr(labels, "target_length", None),
+                     lambda v: min((v + r - 1) // r, al1[4], al2[4]))
+        out = []
+        for name, (a, off, utt, col, steps) in (("alignment1", al1), ("alignment2", al2)):
+            out.append(ImageGroup([f"{name}/{i}" for i in range(k)], a, off, utt, src_len,
+                                  stp_len, col, N, steps, h_src, h_stp))
+        for what, probs, ln, h_ln in (("encoder_self_attention", enc_probs, src_len, h_src),
+                                      ("decoder_self_attention", dec_probs, stp_len, h_stp)):
+            for hop, p in enumerate(probs):
+                _, H, L, _ = p.shape
+                for h in range(H):
+                    out.append(ImageGroup([f"{what}{hop}_head{h}/{i}" for i in range(k)], p,
+                                          h * L * L, H * L * L, ln, ln, L, L, L, h_ln, h_ln))
+        for name, x in (("mel_predicted", mel), ("mel_target", mel_target)):
+            _, T, M = x.shape
+            bins = torch.full((k,), M, dtype=torch.int32, device=dev)
+            out.append(ImageGroup([f"{name}/{i}" for i in range(k)], x, 0, T * M, bins, tgt_len,
+                                  M, M, T, [M] * k, h_tgt))
+        return out
+
+    def _reserve_train_summaries(self, batch) -> None:
+        """Size the recorder's staging slots for this batch shape's plots.  Called on every
+        TRAIN step (integer arithmetic); allocates only when a larger shape is first seen --
+        the step that also allocates that shape's buffers and captures its graph."""
+        from .summary import ImageGroup
+        hp = self.params
+        B, N = batch["source"].shape
+        T, M = batch["mel"].shape[1], batch["mel"].shape[2]
+        r = hp.outputs_per_step
+        q = self.graph_t_quantum if self.graph_cache > 0 else 0
+        Tp = -(-(T // r) // q) * q if q > 0 else T // r
+        k = min(B, 3)
+        need = 256 + 2 * ImageGroup.nbytes(k, N, Tp + 1) + 2 * ImageGroup.nbytes(k, M, Tp * r)
+        self._recorder().reserve(need)
+
+    def _train_summaries(self, batch, features, labels) -> None:
+        """After a TRAIN step (eager or a replay; never inside a capture): queue the step's
+        scalars and, when due, its images, on the training stream (summary.SummaryRecorder)."""
+        from . import summary as S
+        step = self._host_step
+        self._reserve_train_summaries(batch)
+        if self._step_rate is None:
+            self._step_rate = S.StepRate(self._run_option("log_step_count_steps"))
+        rate = self._step_rate.tick(step)
+        every = int(self._run_option("save_summary_steps") or 0)
+        img_every = int(self._run_option("alignment_save_steps") or 0)
+        scalars = every > 0 and step % every == 0
+        images = (img_every > 0 and step % img_every == 0
+                  and bool(self._run_option("save_training_time_metrics")))
+        rec = self._graphs.last_record
+        # the first TRAIN step rehearses a full summary (SummaryRecorder.record, step=None)
+        rehearse = not self._summary_rehearsed and rec is not None and not (scalars and images)
+        if rehearse:
+            self._summary_rehearsed = True
+            want = (scalars, images)
+            scalars = True
+            images = bool(self._run_option("save_training_time_metrics"))
+            self._record_train(None, rec, batch, features, labels, scalars, images, None)
+            scalars, images = want
+        if not (scalars or images) or rec is None:
+            return
+        self._record_train(step, rec, batch, features, labels, scalars, images, rate)
+
+    def _record_train(self, step, rec, batch, features, labels, scalars, images, rate) -> None:
+        out, sv = rec
+        floats, names, groups, extra = [], [], [], {}
+        if scalars:
+            # loss[0:3] = {0.1 L1 + BCE, L1, BCE}; Trainer.scalars = {norm, clip scale, lr, lr_t}
+            code = 0.1 * out["l1"]
+            # (TRAIN is teacher-forced: add_training_stats writes each loss under both tags)
+            floats = [out["loss"], code, code, out["bce"], out["bce"], self._trainer.scalars]
+            names = ["loss_with_teacher", "code_loss", "code_loss_with_teacher", "done_loss",
+                     "done_loss_with_teacher", "global_norm", None, "learning_rate", None]
+            extra = {"l2_regularization_loss": 0.0}
+            if rate is not None:
+                extra["global_step/sec"] = rate
+        if images:
+            # the step's own tensors: under graph_t_quantum their T' is the padded one
+            dec = sv["dec"]
+            Tp, B, N = dec.S2.shape
+            if tuple(dec.AL1.shape) != (Tp + 1, B, N) or B != batch["source"].shape[0]:
+                raise RuntimeError("alignment histories are not [T' + 1, B, N] / [T', B, N]")
+            # (no encoder self-attention plot in TRAIN: the fused attention keeps no
+            # probabilities; EVAL's decode materialises them and plots them)
+            groups = self._image_groups(batch, features, labels, (dec.AL1, B * N, N, B * N, Tp),
+                                        (dec.S2, 0, N, B * N, Tp), sv["mel"], sv["batch"]["mel"])
+        self._recorder().record(step, floats, names, groups, extra)
+
+    def _eval_summaries(self, batch, features, labels, spec) -> None:
+        """EVAL's plots (MetricsSaver with alignment_save_steps = 1, models/models.py:238-247)
+        of an evaluated batch, at the restored global step, into ``model_dir/eval``."""
+        mt = spec.eval_metric_ops
+        B, N = batch["source"].shape
+        als = []
+        for key in ("alignment1", "alignment2"):
+            a = mt[key]                                          # [B, N, T']
+            if tuple(a.shape[:2]) != (B, N):
+                raise RuntimeError(f"{key} is not [B, N, T']")
+            Tp = a.shape[2]
+            als.append((a.transpose(1, 2).contiguous(), 0, Tp * N, N, Tp))
+        probs = {k: [p.contiguous() for p in mt[k] if p is not None]
+                 for k in ("encoder_self_alignments", "decoder_self_alignments")}
+        groups = self._image_groups(batch, features, labels, als[0], als[1],
+                                    spec.predictions["mel"].contiguous(), batch["mel"],
+                                    enc_probs=probs["encoder_self_alignments"],
+                                    dec_probs=probs["decoder_self_alignments"])
+        self._recorder("eval").record(self._host_step, groups=groups)
+
     def _get_trainer(self, batch) -> Trainer:
         """ONE trainer (one optimiser state) for every batch shape: its mask views are re-pointed
         per shape inside one arena (Trainer.reshape), so memory stays flat over a stream of
@@ -361,6 +528,7 @@ class DualSourceSelfAttentionTacotronModel:
         Tp = batch["mel"].shape[1] // self.params.outputs_per_step
         if self._trainer is None:
             self._trainer = Trainer(self.engine, B, N, Tp, seed=self._seed)
+            self._trainer.keep_saved = self.summaries
             if self._pending is not None:
                 # optimiser state, step, seed and status of the restore made before any TRAIN
                 ck, self._pending = self._pending, None
@@ -472,7 +640,10 @@ class DualSourceSelfAttentionTacotronModel:
                    "loss_with_teacher": teach["loss"],
                    "code_loss_with_teacher": 0.1 * teach["l1"],
                    "done_loss_with_teacher": teach["bce"],
-                   "alignment1": out["alignment1"], "alignment2": out["alignment2"]}
+                   "alignment1": out["alignment1"], "alignment2": out["alignment2"],
+                   "l2_regularization_loss": torch.zeros_like(done_loss),
+                   "decoder_self_alignments": out.get("decoder_self_alignments") or [],
+                   "encoder_self_alignments": out.get("encoder_self_alignments") or []}
         return EstimatorSpec(ModeKeys.EVAL, loss=loss, train_op=None,
                              predictions={"mel": out["mel"], "stop_token": out["stop"]},
                              eval_metric_ops=metrics)
@@ -490,10 +661,16 @@ class DualSourceSelfAttentionTacotronModel:
             out = self._graphs.step(batch)
             self._host_step += 1
             self._state_path = None
+            if self.summaries:
+                self._train_summaries(batch, features, labels)
             return EstimatorSpec(mode, loss=out["loss"], train_op=tr.global_step,
                                  predictions=None, eval_metric_ops=None)
         if mode == ModeKeys.EVAL:
-            return self._eval(batch)
+            spec = self._eval(batch)
+            if self.summaries and self._eval_images:
+                self._eval_images = False
+                self._eval_summaries(batch, features, labels, spec)
+            return spec
         raise ValueError(f"Unknown mode: {mode}")
 
     # ---- tf.estimator.Estimator-like drivers
@@ -524,16 +701,35 @@ class DualSourceSelfAttentionTacotronModel:
             if saved_at != self._host_step and steps > 0:
                 self._trainer.snapshot(self.model_dir, keep)
             self._state_path = self._trainer.wait()      # rank 0: the file; others: None
+        if self.summaries:
+            self.flush_summaries()
         return loss
 
     def evaluate(self, input_fn, steps: int = 1, checkpoint_path=None):
+        """``loss`` and the streaming means of the reference's validation metrics
+        (get_validation_metrics, models/models.py:304-320) over ``steps`` batches, with the
+        ``global_step`` of the evaluated state.  With ``summaries``: the metrics, and the plots
+        of the first batch, go to ``model_dir/eval`` at that step."""
+        from .summary import EVAL_METRICS
         self._restore_for(checkpoint_path)
         tot = 0.0
+        sums = dict.fromkeys(EVAL_METRICS, 0.0)
         it = iter(input_fn())
+        self._eval_images = True                   # the first batch's plots (summaries only)
         for _ in range(steps):
             features, labels = next(it)
-            tot += float(self.model_fn(features, labels, ModeKeys.EVAL, self.params).loss.item())
-        return {"loss": tot / steps}
+            spec = self.model_fn(features, labels, ModeKeys.EVAL, self.params)
+            tot += float(spec.loss.item())
+            for k in EVAL_METRICS:
+                sums[k] += float(spec.eval_metric_ops[k].item())
+        out = {"loss": tot / steps}
+        out.update((k, v / steps) for k, v in sums.items())
+        if self.summaries:
+            w = self._recorder("eval")
+            w.writer.add_scalars(self._host_step, out)
+            w.flush()
+        out["global_step"] = self._host_step
+        return out
 
 
 def tacotron_model_factory(hparams, model_dir, run_config, warm_start_from=None, **kw):
@@ -564,3 +760,6 @@ def synthetic_input_fn(params, batch_size: int, N: int = 200, T: int = 1000, sha
                    PreprocessedTargetData(ids, ids, b["mel"], b["target_length"], b["done"],
                                           b["mel_mask"], b["done_mask"]))
     return input_fn
+
+
+from .summary import train_and_evaluate  # noqa: E402,F401  (tf.estimator.train_and_evaluate)

@@ -80,6 +80,9 @@ class Trainer:
                       and self.bucketed else None)
         self._bucket_done = None
         self._snapshotter = None             # checkpoint.Snapshotter, made on first use
+        # summaries (models.py, summaries=True): captured steps then keep the tensors their
+        # forward saved, so the plots can be rendered from a replay's own static buffers
+        self.keep_saved = False
 
     def reshape(self, B: int, N: int, Tp: int) -> None:
         """Point the mask views at a (B, N, T') batch shape."""
@@ -281,6 +284,8 @@ class GraphedStep:
                 self.warm_out = trainer.step(batch)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
+        # (summaries) what the warm-up step produced and saved; taken once by StepGraphCache
+        self.warm_record = (self.warm_out, trainer.last_saved) if trainer.keep_saved else None
         self.split = trainer.world > 1 if split is None else bool(split)
         self.g_fb = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_fb):
@@ -292,6 +297,9 @@ class GraphedStep:
             with torch.cuda.graph(self.g_apply):
                 trainer.apply()
         torch.cuda.synchronize()
+        # (summaries) the capture's own outputs and saved tensors: static buffers of the graph's
+        # pool that every replay rewrites
+        self.record = (self.out, trainer.last_saved) if trainer.keep_saved else None
         # the graph holds raw pointers into the grow-only buffers the step used (the mask
         # arena, the persistent kernels' scratch, the column-reduce / split-K / loss scratch):
         # keep those exact buffers alive for the graph's lifetime, so a later, larger shape
@@ -338,6 +346,9 @@ class StepGraphCache:
         self.t_quantum = int(t_quantum)
         self.entries: "OrderedDict[tuple, tuple]" = OrderedDict()
         self.hits = self.misses = self.evictions = 0
+        # (summaries, Trainer.keep_saved) the last step's (forward outputs, saved tensors): the
+        # eager step's own, or the replayed graph's static buffers
+        self.last_record = None
 
     def _pad_t(self, batch):
         q = self.t_quantum
@@ -365,7 +376,9 @@ class StepGraphCache:
         """One training step on ``batch`` (device tensors); returns {"loss": a tensor that this
         cache does not overwrite later}."""
         if self.size <= 0:
-            return {"loss": self.t.step(batch)["loss"]}
+            out = self.t.step(batch)
+            self.last_record = (out, self.t.last_saved) if self.t.keep_saved else None
+            return {"loss": out["loss"]}
         batch = self._pad_t(batch)
         k = self.key(batch)
         e = self.entries.get(k)
@@ -377,6 +390,7 @@ class StepGraphCache:
             while len(self.entries) > self.size:
                 self.entries.popitem(last=False)
                 self.evictions += 1
+            self.last_record, g.warm_record = g.warm_record, None
             return {"loss": g.warm_out["loss"]}
         self.hits += 1
         self.entries.move_to_end(k)
@@ -386,5 +400,6 @@ class StepGraphCache:
         # GraphedStep.replay() leaves Trainer.shape alone: the next eager step re-views the
         # masks for its own shape (Trainer.reshape), the captured graph keeps its own views
         out = g.replay()
+        self.last_record = g.record
         return {"loss": out["loss"].clone()}
 
