@@ -42,8 +42,9 @@ extern "C" {
  * wgrad_stream / wgrad_ws (deferred weight gradients: sat_mha_bwd_wgrad); 9: the transition agent
  * and cumulative weights of ForwardAttention (trailing fields of SatAttnStep / SatAttnStepBwd,
  * sat_attn_agent_bwd); 10: SatAttnStep.agent_b_sb, the speaker-vector kernels (sat_rows_bias_fwd /
- * _bwd, sat_ctx_tail_fill); 11: the summary image kernels (sat_image_minmax / sat_image_render). */
-#define SAT_ABI_VERSION 11
+ * _bwd, sat_ctx_tail_fill); 11: the summary image kernels (sat_image_minmax / sat_image_render);
+ * 12: the audio front end (SatMelSpec, sat_melspec, sat_mel_stats). */
+#define SAT_ABI_VERSION 12
 
 /* ---------------------------------------------------------------- library */
 int sat_version(void);                         /* 100*major + minor */
@@ -990,6 +991,52 @@ int sat_image_render(const float* src, int64_t src_n, const int64_t* base, const
                      const int32_t* cols, int64_t col_stride, int32_t n_images, int32_t Rmax,
                      int32_t Cmax, const int32_t* rows_host, const int32_t* cols_host,
                      const float* minmax, uint8_t* canvas, void* stream);
+
+/* ---------------------------------------------------------------- audio front end
+ * Waveform to log-mel targets: Audio.melspectrogram (utils/audio.py:51-73) with librosa 0.6 stft
+ * semantics (center=True, reflect padding, a periodic Hann of win_length zero-padded to n_fft),
+ * for a batch of utterances in one launch, and the per-utterance statistics of
+ * preprocess/ljspeech.py:119-131.
+ *   sat_melspec: frame f of utterance b exists for f < frames_b = 1 + lengths[b] / hop.  Its
+ *     samples are ypad[f*hop + j], j < n_fft, ypad being wav[b] reflect-padded by n_fft/2 on both
+ *     sides (taken by index on the unpadded row: i = f*hop + j - n_fft/2, i -> -i below 0,
+ *     i -> 2 (lengths[b] - 1) - i from lengths[b] on).  x = window * samples; X = the n_fft-point
+ *     DFT of x (fp32, in LDS); mag[k] = |X_k| for k < num_freq = n_fft/2 + 1;
+ *     S_m = sum over band_lo[m] <= k < band_hi[m] of basis[m*num_freq + k] * mag[k];
+ *     out[b][f][m] = 20 log10(max(amp_floor, S_m)) - ref_level_db.  mag_out [B][F_max][num_freq]
+ *     (nullable) receives mag.  Rows frames_b <= f < F_max of out and mag_out are written as zeros.
+ *     window [n_fft]; twiddle [n_fft/2][2] = (cos, -sin)(2 pi k / n_fft), computed by the caller in
+ *     fp64 and rounded to fp32, 8-byte aligned; band_lo / band_hi [num_mels] (device int32) bracket
+ *     each basis row's nonzero weights (an all-zero row has lo == hi).  lengths (device int32,
+ *     samples) is what the kernel reads; lengths_host is the caller's HOST copy, which the entry
+ *     checks (a device length the entry would have refused makes that utterance all zero rows).
+ *     Refused before anything is launched -- SAT_ERR_UNSUPPORTED: n_fft not a power of two or
+ *     outside 64..4096; SAT_ERR_ARGUMENT: win > n_fft, hop < 1, num_freq != n_fft/2 + 1, a null
+ *     pointer (mag_out excepted), any lengths[b] <= n_fft/2 (the reflection would run past the
+ *     utterance) or > wav_stride, F_max below the largest frame count, B > 65535.
+ *   sat_mel_stats: out[b][0..3][m] (fp64 [B][4][M]) = min, max, sum and sum of squares of
+ *     mel[b][f][m] over f < min(frames[b], F_max) (device int32); +inf, -inf, 0, 0 when there is no
+ *     frame.  Sums in fp64 in a fixed order; corpus totals are the caller's. */
+typedef struct SatMelSpec {
+  int32_t B, wav_stride;          /* wav [B][wav_stride] */
+  int32_t n_fft, hop, win;
+  int32_t num_mels, num_freq;
+  int32_t F_max;                  /* rows of out / mag_out per utterance */
+  float ref_level_db, amp_floor;
+  const float* wav;
+  const int32_t* lengths;         /* device */
+  const int32_t* lengths_host;    /* host */
+  const float* window;
+  const float* twiddle;
+  const float* basis;             /* [num_mels][num_freq] dense */
+  const int32_t* band_lo;
+  const int32_t* band_hi;
+  float* out;                     /* [B][F_max][num_mels] */
+  float* mag_out;                 /* [B][F_max][num_freq] or NULL */
+} SatMelSpec;
+int sat_melspec(const SatMelSpec* d, void* stream);
+int sat_mel_stats(const float* mel, const int32_t* frames, int32_t B, int32_t F_max, int32_t M,
+                  double* out, void* stream);
 
 /* ---------------------------------------------------------------- dataset records (host)
  * TFRecord framing of the dataset path: datasets/ljspeech/dataset.py:96-112 reads

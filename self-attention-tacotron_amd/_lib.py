@@ -191,6 +191,11 @@ SatAttnStep = _struct("SatAttnStep", """
     ptr:s_out ptr:a_out ptr:s2_out ptr:ctx i64:ctx_sb ptr:stats ptr:loc_out i32:lpp i32:phases
     ptr:u_prev ptr:u_out ptr:agent_w ptr:agent_b ptr:state_out i64:agent_b_sb""")
 
+SatMelSpec = _struct("SatMelSpec", """
+    i32:B i32:wav_stride i32:n_fft i32:hop i32:win i32:num_mels i32:num_freq i32:F_max
+    f32:ref_level_db f32:amp_floor ptr:wav ptr:lengths ptr:lengths_host ptr:window ptr:twiddle
+    ptr:basis ptr:band_lo ptr:band_hi ptr:out ptr:mag_out""")
+
 # name -> argtypes (restype is int for all but sat_last_error_string)
 SIGNATURES = {
     "sat_version": [],
@@ -275,6 +280,8 @@ SIGNATURES.update({
     "sat_arena_digest": [_P, _I64, _I64, _I32, _P, _P],
     "sat_image_minmax": [_P, _I64, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     "sat_image_render": [_P, _I64, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P],
+    "sat_melspec": [ctypes.POINTER(SatMelSpec), _P],
+    "sat_mel_stats": [_P, _P, _I32, _I32, _I32, _P, _P],
 })
 
 RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
@@ -296,7 +303,7 @@ RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
 
 _lib: Optional[ctypes.CDLL] = None
 # include/sat_abi.h SAT_ABI_VERSION this binding's structs follow
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 def load(path: str = LIB_PATH) -> ctypes.CDLL:

@@ -1,0 +1,223 @@
+"""Audio front end: ``utils/audio.py`` without librosa / scipy.
+
+``Audio(hparams)`` keeps the reference's surface (``utils/audio.py:23-73``): ``_stft_parameters``,
+``_build_mel_basis``, ``load_wav``, ``save_wav``, ``melspectrogram``, ``normalize_mel``,
+``_amp_to_db``, ``_linear_to_mel``.  The feature extraction itself -- reflect padding, framing,
+window, FFT, magnitude, mel projection, dB -- is one libsat_hip launch (``csrc/audio.hip``) for a
+whole batch of utterances (``melspectrogram_batch``); torch only allocates and copies.  There is
+no host fallback: without the library or a GPU ``melspectrogram`` raises.
+
+Not carried over: ``trim`` (librosa.effects.trim, used only by the VCTK preprocessing) and
+resampling in ``load_wav`` (a file at another rate raises ``ValueError``).
+"""
+
+from __future__ import annotations
+
+import wave
+
+import numpy as np
+
+AMP_FLOOR = 1e-5            # utils/audio.py:73
+
+
+def hz_to_mel(f):
+    """Slaney scale: linear at 200/3 Hz per mel below 1000 Hz, logarithmic above (step ln 6.4 / 27)."""
+    f = np.asarray(f, np.float64)
+    f_sp, min_log_hz = 200.0 / 3.0, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, np.log(6.4) / 27.0
+    return np.where(f >= min_log_hz,
+                    min_log_mel + np.log(np.maximum(f, min_log_hz) / min_log_hz) / logstep,
+                    f / f_sp)
+
+
+def mel_to_hz(m):
+    m = np.asarray(m, np.float64)
+    f_sp, min_log_hz = 200.0 / 3.0, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, np.log(6.4) / 27.0
+    return np.where(m >= min_log_mel, min_log_hz * np.exp(logstep * (m - min_log_mel)), f_sp * m)
+
+
+def mel_filterbank(sr: int, n_fft: int, n_mels: int) -> np.ndarray:
+    """``librosa.filters.mel(sr, n_fft, n_mels)`` at its defaults (fmin 0, fmax sr/2, Slaney scale
+    and area normalisation): triangles between consecutive mel points, row i scaled by
+    2 / (f[i+2] - f[i]).  Computed in float64, returned as float32 [n_mels, n_fft/2 + 1]."""
+    fftfreqs = np.linspace(0.0, sr / 2.0, 1 + n_fft // 2)
+    mel_f = mel_to_hz(np.linspace(hz_to_mel(0.0), hz_to_mel(sr / 2.0), n_mels + 2))
+    fdiff = np.diff(mel_f)
+    ramps = mel_f[:, None] - fftfreqs[None, :]
+    lower = -ramps[:-2] / fdiff[:-1, None]
+    upper = ramps[2:] / fdiff[1:, None]
+    weights = np.maximum(0.0, np.minimum(lower, upper))
+    weights *= (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, None]
+    return weights.astype(np.float32)
+
+
+def band_limits(basis: np.ndarray):
+    """First bin with a nonzero weight and one past the last, per row (lo == hi: an empty row)."""
+    nz = basis != 0
+    any_ = nz.any(axis=1)
+    lo = np.where(any_, nz.argmax(axis=1), 0)
+    hi = np.where(any_, basis.shape[1] - nz[:, ::-1].argmax(axis=1), 0)
+    return lo.astype(np.int32), hi.astype(np.int32)
+
+
+def hann_window(win_length: int, n_fft: int) -> np.ndarray:
+    """Periodic Hann of ``win_length`` centred in ``n_fft`` ((n_fft - win) // 2 zeros in front),
+    as librosa's stft pads its window."""
+    n = np.arange(win_length, dtype=np.float64)
+    w = np.zeros(n_fft, np.float64)
+    off = (n_fft - win_length) // 2
+    w[off:off + win_length] = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / win_length)
+    return w.astype(np.float32)
+
+
+def twiddle_table(n_fft: int) -> np.ndarray:
+    """exp(-2 pi i k / n_fft), k < n_fft/2, as float32 [n_fft/2, 2] rounded from float64; the
+    quarter-turn entry is exactly (0, -1)."""
+    k = np.arange(n_fft // 2, dtype=np.float64)
+    t = np.stack([np.cos(2.0 * np.pi * k / n_fft), -np.sin(2.0 * np.pi * k / n_fft)], axis=1)
+    t[0] = (1.0, 0.0)
+    t[n_fft // 4] = (0.0, -1.0)
+    return t.astype(np.float32)
+
+
+class Audio:
+    def __init__(self, hparams, device=None):
+        self.hparams = hparams
+        self._mel_basis = self._build_mel_basis()
+        self.average_mel_level_db = np.array(hparams.average_mel_level_db, dtype=np.float32)
+        self.stddev_mel_level_db = np.array(hparams.stddev_mel_level_db, dtype=np.float32)
+        self._device = device
+        self._plans = {}            # (n_fft, win, device) -> device-side tables
+
+    # ------------------------------------------------------------------ reference surface
+    def _build_mel_basis(self):
+        n_fft = (self.hparams.num_freq - 1) * 2
+        return mel_filterbank(self.hparams.sample_rate, n_fft, self.hparams.num_mels)
+
+    def _stft_parameters(self):
+        n_fft = (self.hparams.num_freq - 1) * 2
+        hop_length = int(self.hparams.frame_shift_ms / 1000 * self.hparams.sample_rate)
+        win_length = int(self.hparams.frame_length_ms / 1000 * self.hparams.sample_rate)
+        return n_fft, hop_length, win_length
+
+    def load_wav(self, path):
+        """16-bit PCM through the standard ``wave`` module: float32 in [-1, 1) (``/ 32768``),
+        channels averaged.  No resampling: another rate than hparams.sample_rate is an error."""
+        with wave.open(path, "rb") as f:
+            rate, width, channels = f.getframerate(), f.getsampwidth(), f.getnchannels()
+            raw = f.readframes(f.getnframes())
+        if rate != self.hparams.sample_rate:
+            raise ValueError(f"{path}: sample rate {rate} Hz, hparams.sample_rate is "
+                             f"{self.hparams.sample_rate} Hz (no resampler: convert the file)")
+        if width != 2:
+            raise ValueError(f"{path}: {8 * width}-bit samples, only 16-bit PCM is read")
+        y = np.frombuffer(raw, "<i2").astype(np.float32) / np.float32(32768.0)
+        if channels > 1:
+            y = y.reshape(-1, channels).mean(axis=1, dtype=np.float32)
+        return y
+
+    def save_wav(self, wav, path):
+        """16-bit PCM mono at hparams.sample_rate; floats are scaled by 32768 and clipped."""
+        wav = np.asarray(wav)
+        if wav.dtype != np.int16:
+            wav = np.clip(np.rint(wav.astype(np.float64) * 32768.0), -32768, 32767).astype("<i2")
+        with wave.open(path, "wb") as f:
+            f.setnchannels(1)
+            f.setsampwidth(2)
+            f.setframerate(int(self.hparams.sample_rate))
+            f.writeframes(wav.astype("<i2").tobytes())
+
+    def melspectrogram(self, y):
+        """[num_mels, frames] like the reference; numpy in, numpy out -- device tensor in, device
+        tensor out."""
+        import torch
+        mel, frames = self.melspectrogram_batch([y])
+        if isinstance(y, torch.Tensor):
+            from . import kernels as K
+            return K.transpose(mel[0])
+        return np.ascontiguousarray(mel[0].cpu().numpy().T)
+
+    def normalize_mel(self, S):
+        return (S - self.average_mel_level_db) / self.stddev_mel_level_db
+
+    def _linear_to_mel(self, spectrogram):
+        return np.dot(self._mel_basis, spectrogram)
+
+    def _amp_to_db(self, x):
+        return 20 * np.log10(np.maximum(AMP_FLOOR, x))
+
+    # ------------------------------------------------------------------ the GPU path
+    def _dev(self):
+        import torch
+        if self._device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("Audio.melspectrogram runs on the GPU (libsat_hip); none found")
+            self._device = torch.device("cuda", torch.cuda.current_device())
+        return self._device
+
+    def _plan(self, device):
+        """Device-side tables of this (n_fft, win) configuration, built once per device."""
+        import torch
+        n_fft, hop, win = self._stft_parameters()
+        key = (n_fft, win, str(device))
+        plan = self._plans.get(key)
+        if plan is None:
+            lo, hi = band_limits(self._mel_basis)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            if win > n_fft:
+                raise ValueError(f"frame_length_ms gives a window of {win} samples, longer than "
+                                 f"n_fft = {n_fft}")
+            plan = {"window": up(hann_window(win, n_fft)),
+                    "twiddle": up(twiddle_table(n_fft)), "basis": up(self._mel_basis),
+                    "band_lo": up(lo), "band_hi": up(hi)}
+            self._plans[key] = plan
+        return plan
+
+    def melspectrogram_batch(self, wavs, return_magnitudes: bool = False):
+        """A list of 1-D waveforms (numpy arrays or tensors) through one padded upload and one
+        launch: ``(mel [B, F_max, num_mels], frames [B] int32)`` on the device, rows past an
+        utterance's frame count zero; with ``return_magnitudes`` also ``[B, F_max, num_freq]``."""
+        import torch
+        from . import kernels as K
+        if len(wavs) == 0:
+            raise ValueError("melspectrogram_batch: no waveform")
+        n_fft, hop, win = self._stft_parameters()
+        if hop < 1:
+            raise ValueError(f"frame_shift_ms gives a hop of {hop} samples")
+        on_dev = [isinstance(w, torch.Tensor) for w in wavs]
+        device = wavs[0].device if on_dev[0] and wavs[0].is_cuda else self._dev()
+        lengths = [int(w.shape[0]) for w in wavs]
+        if any(w.ndim != 1 for w in wavs):
+            raise ValueError("melspectrogram_batch: waveforms must be 1-D")
+        B, stride = len(wavs), max(lengths)
+        frames = [1 + L // hop for L in lengths]
+        F_max = max(frames)
+        if all(on_dev):
+            wav = K.zeros(B, stride, device=device)
+            for b, w in enumerate(wavs):
+                wav[b, :lengths[b]].copy_(w)
+        else:
+            host = np.zeros((B, stride), np.float32)
+            for b, w in enumerate(wavs):
+                host[b, :lengths[b]] = w.cpu().numpy() if on_dev[b] else w
+            wav = torch.from_numpy(host).to(device)
+        meta = torch.from_numpy(np.array([lengths, frames], np.int32)).to(device)
+        plan = self._plan(device)
+        out = torch.empty(B, F_max, self.hparams.num_mels, device=device)
+        mag = torch.empty(B, F_max, self.hparams.num_freq, device=device) \
+            if return_magnitudes else None
+        K.melspec(wav, meta[0], lengths, n_fft=n_fft, hop=hop, win=win, window=plan["window"],
+                  twiddle=plan["twiddle"], basis=plan["basis"], band_lo=plan["band_lo"],
+                  band_hi=plan["band_hi"], ref_level_db=self.hparams.ref_level_db,
+                  amp_floor=AMP_FLOOR, out=out, mag_out=mag)
+        return (out, meta[1], mag) if return_magnitudes else (out, meta[1])
+
+    def mel_statistics(self, mel, frames):
+        """Per-utterance min, max, sum and sum of squares per mel bin over the valid frames:
+        float64 [B, 4, num_mels] on the device (preprocess/ljspeech.py:125-131)."""
+        import torch
+        from . import kernels as K
+        out = torch.empty(mel.shape[0], 4, mel.shape[2], dtype=torch.float64, device=mel.device)
+        K.mel_stats(mel, frames, out)
+        return out

@@ -1,0 +1,222 @@
+// Audio front end: waveform -> log-mel targets (utils/audio.py:51-73 with librosa 0.6 stft
+// semantics) and the per-utterance mel statistics of preprocess/ljspeech.py:119-131.
+//
+// sat_melspec: one workgroup of 256 threads per PAIR of frames of one utterance.  The two windowed
+// frames x0, x1 are the real and imaginary part of one complex n_fft-point FFT z = x0 + i x1 held
+// in LDS (radix-2 decimation in time: the gather from the waveform writes bit-reversed, log2(n_fft)
+// butterfly passes follow); the spectra separate as X0[k] = (Z[k] + conj Z[n-k]) / 2 and
+// X1[k] = (Z[k] - conj Z[n-k]) / 2i, which costs no further twiddle.  Magnitudes replace the
+// twiddle table in LDS, the band sums read them there, and only num_mels floats per frame leave
+// the chip.  LDS per workgroup: 8 n_fft (z) + 4 n_fft + 8 (twiddles, then 2 x (n_fft/2 + 1)
+// magnitudes) = 12 n_fft + 8 bytes: 24 KB at 2048 (6 workgroups per CU), 48 KB at 4096 (3).
+// The separation, the magnitude, the band sum and the logarithm are done in fp64 (a few hundred
+// operations per frame beside the 11 k butterflies), so the FFT's own fp32 rounding is the only
+// error of the result -- DESIGN.md "Audio front end".
+#include "sat_common.h"
+
+using namespace sat;
+
+namespace {
+
+struct MelSpecP {
+  const float* wav; const int32_t* lengths;
+  const float* window; const float2* twiddle;
+  const float* basis; const int32_t* band_lo; const int32_t* band_hi;
+  float* out; float* mag_out;
+  int B, wav_stride, n_fft, log2n, hop, num_mels, num_freq, F_max;
+  float ref_level_db, amp_floor;
+};
+
+// sample j of frame f of the utterance reflect-padded by n_fft/2 on both sides, by index on the
+// unpadded row: i = f*hop + j - n_fft/2, mirrored about 0 (i -> -i) or about L-1 (i -> 2(L-1)-i).
+// With n_fft/2 < L and f <= L/hop one mirror always lands inside [0, L).
+__device__ __forceinline__ int reflect_index(int f, int j, int hop, int half_n, int L) {
+  int i = f * hop + j - half_n;
+  if (i < 0) i = -i;
+  if (i >= L) i = 2 * (L - 1) - i;
+  return i;
+}
+
+__global__ void __launch_bounds__(256) melspec_kernel(MelSpecP p) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int n = p.n_fft, half_n = n >> 1, nf = p.num_freq, tid = threadIdx.x;
+  float2* z = reinterpret_cast<float2*>(smem_raw);
+  float2* tw = z + n;                                   // half_n twiddles
+  float* mag = reinterpret_cast<float*>(tw);            // later: 2 x nf magnitudes
+  const int b = blockIdx.y, f0 = 2 * blockIdx.x, f1 = f0 + 1;
+
+  // a length the entry would have refused (device copy out of step with the host's) reads nothing
+  int L = p.lengths[b];
+  int frames = (L > half_n && L <= p.wav_stride) ? 1 + L / p.hop : 0;
+  if (frames > p.F_max) frames = p.F_max;
+  float* out0 = p.out + ((int64_t)b * p.F_max + f0) * p.num_mels;
+  float* mag0 = p.mag_out ? p.mag_out + ((int64_t)b * p.F_max + f0) * nf : nullptr;
+  const bool row1 = f1 < p.F_max;                       // the pair's second row exists at all
+
+  if (f0 >= frames) {                                   // both rows are padding: zeros
+    const int rows = row1 ? 2 : 1;
+    for (int i = tid; i < rows * p.num_mels; i += 256) out0[i] = 0.f;
+    if (mag0)
+      for (int i = tid; i < rows * nf; i += 256) mag0[i] = 0.f;
+    return;
+  }
+  const bool have1 = f1 < frames;
+
+  const float* y = p.wav + (int64_t)b * p.wav_stride;
+  const int shift = 32 - p.log2n;
+  for (int j = tid; j < n; j += 256) {
+    const float w = p.window[j];
+    float v0 = 0.f, v1 = 0.f;
+    if (w != 0.f) {
+      v0 = w * y[reflect_index(f0, j, p.hop, half_n, L)];
+      if (have1) v1 = w * y[reflect_index(f1, j, p.hop, half_n, L)];
+    }
+    z[__brev((unsigned)j) >> shift] = make_float2(v0, v1);
+  }
+  for (int j = tid; j < half_n; j += 256) tw[j] = p.twiddle[j];
+  __syncthreads();
+
+  for (int s = 0; s < p.log2n; ++s) {
+    const int half = 1 << s, tshift = p.log2n - 1 - s;
+    for (int j = tid; j < half_n; j += 256) {
+      const int pos = j & (half - 1);
+      const int i0 = ((j >> s) << (s + 1)) + pos, i1 = i0 + half;
+      const float2 w = tw[pos << tshift];
+      const float2 a = z[i0], c = z[i1];
+      const float tr = c.x * w.x - c.y * w.y, ti = c.x * w.y + c.y * w.x;
+      z[i0] = make_float2(a.x + tr, a.y + ti);
+      z[i1] = make_float2(a.x - tr, a.y - ti);
+    }
+    __syncthreads();
+  }
+
+  // the last pass's barrier also released the twiddles: magnitudes take their place
+  for (int k = tid; k < nf; k += 256) {
+    const float2 a = z[k], c = z[(n - k) & (n - 1)];
+    const double r0 = 0.5 * ((double)a.x + c.x), i0 = 0.5 * ((double)a.y - c.y);
+    const double r1 = 0.5 * ((double)a.y + c.y), i1 = 0.5 * ((double)c.x - a.x);
+    const float m0 = (float)sqrt(r0 * r0 + i0 * i0);
+    const float m1 = have1 ? (float)sqrt(r1 * r1 + i1 * i1) : 0.f;
+    mag[k] = m0;
+    mag[nf + k] = m1;
+    if (mag0) {
+      mag0[k] = m0;
+      if (row1) mag0[nf + k] = m1;
+    }
+  }
+  __syncthreads();
+
+  for (int t = tid; t < 2 * p.num_mels; t += 256) {
+    const int fr = t >= p.num_mels, m = t - fr * p.num_mels;
+    if (fr && !row1) continue;
+    float v = 0.f;
+    if (!fr || have1) {
+      int lo = p.band_lo[m], hi = p.band_hi[m];
+      lo = lo < 0 ? 0 : lo;
+      hi = hi > nf ? nf : hi;
+      const float* wrow = p.basis + (int64_t)m * nf;
+      const float* mg = mag + fr * nf;
+      double acc = 0.0;
+      for (int k = lo; k < hi; ++k) acc += (double)wrow[k] * (double)mg[k];
+      const double fl = (double)p.amp_floor;
+      v = (float)(20.0 * log10(acc > fl ? acc : fl) - (double)p.ref_level_db);
+    }
+    out0[fr * p.num_mels + m] = v;
+  }
+}
+
+struct MelStatsP {
+  const float* mel; const int32_t* frames; double* out;
+  int B, F_max, M;
+};
+
+// One block per (utterance, 16 mel bins): 16 frame slices x 16 bins.  Each slice folds its frames
+// f = slice, slice + 16, .. (sums in fp64), one thread per bin then folds the 16 slices in a fixed
+// order: no atomics, the same bits on every run.
+__global__ void __launch_bounds__(256) mel_stats_kernel(MelStatsP p) {
+  __shared__ double part[16][16][4];
+  const int b = blockIdx.y;
+  const int cg = threadIdx.x & 15, slice = threadIdx.x >> 4;
+  const int m = blockIdx.x * 16 + cg;
+  int rows = p.frames[b];
+  rows = rows < 0 ? 0 : (rows > p.F_max ? p.F_max : rows);
+  double mn = INFINITY, mx = -INFINITY, s1 = 0.0, s2 = 0.0;
+  if (m < p.M) {
+    const float* base = p.mel + (int64_t)b * p.F_max * p.M + m;
+    for (int f = slice; f < rows; f += 16) {
+      const double v = base[(int64_t)f * p.M];
+      mn = v < mn ? v : mn;
+      mx = v > mx ? v : mx;
+      s1 += v;
+      s2 += v * v;
+    }
+  }
+  part[slice][cg][0] = mn; part[slice][cg][1] = mx;
+  part[slice][cg][2] = s1; part[slice][cg][3] = s2;
+  __syncthreads();
+  if (slice == 0 && m < p.M) {
+    for (int k = 1; k < 16; ++k) {
+      mn = part[k][cg][0] < mn ? part[k][cg][0] : mn;
+      mx = part[k][cg][1] > mx ? part[k][cg][1] : mx;
+      s1 += part[k][cg][2];
+      s2 += part[k][cg][3];
+    }
+    double* o = p.out + (int64_t)b * 4 * p.M + m;
+    o[0] = mn; o[p.M] = mx; o[2 * p.M] = s1; o[3 * p.M] = s2;
+  }
+}
+
+}  // namespace
+
+extern "C" int sat_melspec(const SatMelSpec* d, void* stream) {
+  SAT_CHECK_ARG(d, "sat_melspec: null descriptor");
+  const int n = d->n_fft;
+  if (n < 64 || n > 4096 || (n & (n - 1)) != 0) {
+    set_error("sat_melspec: n_fft %d is not a power of two in 64..4096", n);
+    return SAT_ERR_UNSUPPORTED;
+  }
+  SAT_CHECK_ARG(d->win >= 1 && d->win <= n, "sat_melspec: win %d outside 1..n_fft %d", d->win, n);
+  SAT_CHECK_ARG(d->hop >= 1, "sat_melspec: hop %d < 1", d->hop);
+  SAT_CHECK_ARG(d->num_freq == n / 2 + 1, "sat_melspec: num_freq %d != n_fft/2 + 1 = %d",
+                d->num_freq, n / 2 + 1);
+  SAT_CHECK_ARG(d->B >= 0 && d->B <= 65535 && d->num_mels >= 1 && d->wav_stride >= 0 &&
+                d->F_max >= 0, "sat_melspec: bad sizes");
+  if (d->B == 0) return SAT_OK;
+  SAT_CHECK_ARG(d->wav && d->lengths && d->lengths_host && d->window && d->twiddle && d->basis &&
+                d->band_lo && d->band_hi && d->out, "sat_melspec: null pointer");
+  SAT_CHECK_ARG((reinterpret_cast<uintptr_t>(d->twiddle) & 7) == 0,
+                "sat_melspec: twiddle table must be 8-byte aligned");
+  int max_frames = 0;
+  for (int b = 0; b < d->B; ++b) {
+    const int L = d->lengths_host[b];
+    SAT_CHECK_ARG(L > n / 2, "sat_melspec: lengths[%d] = %d <= n_fft/2 = %d (the reflection would "
+                  "run past the utterance)", b, L, n / 2);
+    SAT_CHECK_ARG(L <= d->wav_stride, "sat_melspec: lengths[%d] = %d > wav_stride %d", b, L,
+                  d->wav_stride);
+    max_frames = std::max(max_frames, 1 + L / d->hop);
+  }
+  SAT_CHECK_ARG(d->F_max >= max_frames, "sat_melspec: F_max %d < the largest frame count %d",
+                d->F_max, max_frames);
+  int log2n = 0;
+  while ((1 << log2n) < n) ++log2n;
+  MelSpecP p{d->wav, d->lengths, d->window, reinterpret_cast<const float2*>(d->twiddle), d->basis,
+             d->band_lo, d->band_hi, d->out, d->mag_out, d->B, d->wav_stride, n, log2n, d->hop,
+             d->num_mels, d->num_freq, d->F_max, d->ref_level_db, d->amp_floor};
+  const size_t lds = (size_t)12 * n + 8;
+  hipLaunchKernelGGL(melspec_kernel, dim3((d->F_max + 1) / 2, d->B), dim3(256), lds,
+                     as_stream(stream), p);
+  SAT_LAUNCH_CHECK("sat_melspec");
+  return SAT_OK;
+}
+
+extern "C" int sat_mel_stats(const float* mel, const int32_t* frames, int32_t B, int32_t F_max,
+                             int32_t M, double* out, void* stream) {
+  SAT_CHECK_ARG(B >= 0 && B <= 65535 && F_max >= 0 && M >= 1, "sat_mel_stats: bad sizes");
+  if (B == 0) return SAT_OK;
+  SAT_CHECK_ARG(frames && out && (mel || F_max == 0), "sat_mel_stats: null pointer");
+  SAT_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 7) == 0, "sat_mel_stats: out must be 8-byte aligned");
+  MelStatsP p{mel, frames, out, B, F_max, M};
+  hipLaunchKernelGGL(mel_stats_kernel, dim3((M + 15) / 16, B), dim3(256), 0, as_stream(stream), p);
+  SAT_LAUNCH_CHECK("sat_mel_stats");
+  return SAT_OK;
+}

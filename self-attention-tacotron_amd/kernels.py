@@ -1096,3 +1096,52 @@ def image_render(src, base, rows, cols, col_stride, minmax, canvas, rows_host=No
     if minmax.numel() < 2 * I:
         raise ValueError("image_render: minmax too small")
     _lib.call("sat_image_render", *args, _p(minmax), _p(canvas), _stream())
+
+
+# ---- audio front end (csrc/audio.hip; sat_amd/audio.py)
+def melspec(wav, lengths, lengths_host, *, n_fft, hop, win, window, twiddle, basis, band_lo,
+            band_hi, ref_level_db, amp_floor, out, mag_out=None):
+    """Batch of waveforms ``wav`` [B, stride] -> mel dB ``out`` [B, F_max, num_mels] (and the
+    magnitudes ``mag_out`` [B, F_max, num_freq]) in one launch; see include/sat_abi.h.  Only
+    dtypes and buffer sizes are checked here: what the entry refuses, it refuses itself."""
+    for name, t in (("wav", wav), ("window", window), ("twiddle", twiddle), ("basis", basis),
+                    ("out", out), ("mag_out", mag_out)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"melspec: {name} must be a contiguous float32 tensor")
+    for name, t in (("lengths", lengths), ("band_lo", band_lo), ("band_hi", band_hi)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f"melspec: {name} must be a contiguous int32 tensor")
+    if wav.dim() != 2 or basis.dim() != 2 or out.dim() != 3:
+        raise ValueError("melspec: wav [B, stride], basis [num_mels, num_freq], out [B, F, num_mels]")
+    B, stride = wav.shape
+    num_mels, num_freq = basis.shape
+    F_max = out.shape[1]
+    if out.shape != (B, F_max, num_mels) or (mag_out is not None
+                                             and mag_out.shape != (B, F_max, num_freq)):
+        raise ValueError("melspec: out [B, F, num_mels] / mag_out [B, F, num_freq] expected")
+    if (lengths.numel() != B or len(lengths_host) != B or band_lo.numel() != num_mels
+            or band_hi.numel() != num_mels):
+        raise ValueError("melspec: lengths need B entries, band_lo / band_hi num_mels entries")
+    if window.numel() < n_fft or twiddle.numel() < n_fft:
+        raise ValueError("melspec: window and twiddle table need n_fft floats each")
+    keep, host = _host_i32(lengths_host, B)
+    d = _lib.SatMelSpec(B=B, wav_stride=stride, n_fft=int(n_fft), hop=int(hop), win=int(win),
+                        num_mels=num_mels, num_freq=num_freq, F_max=F_max,
+                        ref_level_db=float(ref_level_db), amp_floor=float(amp_floor),
+                        wav=_p(wav), lengths=_p(lengths), lengths_host=host, window=_p(window),
+                        twiddle=_p(twiddle), basis=_p(basis), band_lo=_p(band_lo),
+                        band_hi=_p(band_hi), out=_p(out), mag_out=_p(mag_out) or None)
+    _lib.check(_lib.load().sat_melspec(ctypes.byref(d), _stream()), "sat_melspec")
+
+
+def mel_stats(mel, frames, out):
+    """``out`` [B, 4, M] float64 = min, max, sum, sum of squares of ``mel`` [B, F_max, M] over each
+    utterance's first ``frames`` [B] (int32) rows."""
+    if mel.dtype != torch.float32 or not mel.is_contiguous() or mel.dim() != 3:
+        raise ValueError("mel_stats: mel must be a contiguous float32 [B, F_max, M] tensor")
+    B, F_max, M = mel.shape
+    if frames.dtype != torch.int32 or not frames.is_contiguous() or frames.numel() != B:
+        raise ValueError("mel_stats: frames must be a contiguous int32 [B] tensor")
+    if out.dtype != torch.float64 or not out.is_contiguous() or out.shape != (B, 4, M):
+        raise ValueError("mel_stats: out must be a contiguous float64 [B, 4, M] tensor")
+    _lib.call("sat_mel_stats", _p(mel), _p(frames), B, F_max, M, _p(out), _stream())
