@@ -125,7 +125,7 @@ typedef struct SatGemmDesc {
    * non-contiguous dimension), i.e. C = A[:, :k1] B + A[:, k1:] B2 -- with A2 set too, A B + A2 B2:
    * a sum of two products of different operands as ONE reduction.  Same constraints as A2 (B2
    * offset by B's batch strides).  NULL = off.
-   * A2 / B2 outside those constraints (k1 % 32 != 0, SAT_GEMM_LDS=0, operands not vector-
+   * A2 / B2 outside those constraints (k1 % 32 != 0, operands not vector-
    * loadable): two accumulating launches instead (C = A[:, :k1] B[:k1] + beta C + bias + add,
    * then C += the k >= k1 part), which needs a linear epilogue (no act / mul / C2). */
   const float* B2;
@@ -629,7 +629,9 @@ typedef struct SatDecAttnFwd {
   float* S1; float* AL1; float* S2; float* ST; float* LOC;
   float* E; float* PART; float* QP; uint32_t* ctr; int32_t* err;
   int64_t* prof;   /* optional [256][16] per-workgroup segment clocks (100 MHz) followed by a
-                      [T][256][4] event trace, NULL = off */
+                      [T][256][4] event trace, NULL = off; written only by builds with
+                      -DSAT_FWD8_TRACE=1 or -DSAT_SEGMENT_CLOCKS=1 (the production build reads
+                      no clock and leaves the buffer untouched) */
   float* ZH;       /* optional [T][B][N][D1+D2]: tanh of every energy pre-activation, kept for
                       sat_decoder_attention_bwd (which then recomputes no transcendental) */
 } SatDecAttnFwd;

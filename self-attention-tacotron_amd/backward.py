@@ -11,7 +11,6 @@ recurrence (dW = sum_t x_t^T dgates_t).
 from __future__ import annotations
 
 import math
-import os
 from typing import Dict
 
 import torch
@@ -42,23 +41,16 @@ class Aux:
         with torch.cuda.stream(self.s):
             fn()
 
-    def run_side(self, fn, *tensors, which: int = 2):
-        """run a branch on a stream of its own (K.aux_stream index 2, or ``which``), forked here
-        from the main stream and joined with the others: it does not queue behind the aux
-        backlog"""
-        s = K.aux_stream(self.dev, which)
+    def run_side(self, fn, *tensors):
+        """run a branch on a stream of its own (K.aux_stream index 2), forked here from the main
+        stream and joined with the others: it does not queue behind the aux backlog"""
+        s = K.aux_stream(self.dev, 2)
         s.wait_stream(torch.cuda.current_stream())
         if s not in self.used:
             self.used.append(s)
         self.keep.extend(tensors)
         with torch.cuda.stream(s):
             fn()
-
-    def switch(self):
-        """Later branches on a further stream, so they do not queue behind the branches issued
-        so far (the decoder's weight-gradient backlog)."""
-        self.s = K.aux_stream(self.dev, 1)
-        self.used.append(self.s)
 
     def join(self):
         for s in self.used:
@@ -93,45 +85,23 @@ def lin_bwd(x, dy, W, dW, db, ws, dx=None, beta_dx=0.0, need_dx=True, aux=None):
 
 
 # the attention parameter pass's T steps in PG_TSPLIT ranges per position (sat_attn_param_grads
-# tsplit): 1600 one-position workgroups at 3 waves per SIMD leave the third residency round
-# nearly empty; SAT_PG_TSPLIT=1 is the unsplit A/B arm
-PG_TSPLIT = int(os.environ.get("SAT_PG_TSPLIT", "3"))
-# SAT_WGRAD_BATCH=1: the decoder LSTM kernels' weight-gradient blocks as one batched launch per
-# kernel -- measured slower (13.80 -> 13.96 ms/step: its larger grid crowds out the encoder
-# backward's short launches beside it; profiles/r05r_wgrad_batch_ab.txt)
-WGRAD_BATCH = os.environ.get("SAT_WGRAD_BATCH", "0") == "1"
-
-# SAT_MHA_WGRAD_AUX=1 runs a multi-head attention's four weight gradients on the aux stream
-# (sat_mha_bwd_wgrad after a weight-deferred sat_mha_bwd).  Off: measured +0.45 ms/step for both
-# hops (the tail's aux branch is the longer one already) and neutral for the decoder head alone
-# (profiles/r05n_mha_wgrad_aux_ab.txt) -- the LSTM stack's BPTT waits for the aux join anyway.
-MHA_WGRAD_AUX = os.environ.get("SAT_MHA_WGRAD_AUX", "0") == "1"
+# tsplit): unsplit, 1600 one-position workgroups at 3 waves per SIMD leave the third residency
+# round nearly empty
+PG_TSPLIT = 3
 
 
-def mha_bwd(P, G, scope, s, dy, ws, aux=None):
-    """Backward of model.mha_fwd: ONE sat_mha_bwd call.  Returns dx [B, L, W].  With ``aux`` the
-    four weight gradients are deferred to sat_mha_bwd_wgrad on the aux stream."""
+def mha_bwd(P, G, scope, s, dy, ws):
+    """Backward of model.mha_fwd: ONE sat_mha_bwd call, weight gradients included (deferring
+    them to the aux stream measured slower: the tail's aux branch is the longer one already).
+    Returns dx [B, L, W]."""
     names = [f"{scope}/{n}_projection/{t}" for n in ("query", "key", "value", "output")
              for t in ("kernel", "bias")]
-    d, scratch = K.mha_desc(s["x"], *(P[n] for n in names), s["heads"], s["causal"], s["mask"], s)
+    d, _ = K.mha_desc(s["x"], *(P[n] for n in names), s["heads"], s["causal"], s["mask"], s)
     dx = torch.empty_like(s["x"])
     dyc = K.contiguous(dy)
     d.dy, d.dx = dyc.data_ptr(), dx.data_ptr()
-    grads = [G[n].data_ptr() for n in names]
-    defer = aux is not None and MHA_WGRAD_AUX and dy.is_cuda
-    if not defer:
-        d.dWq, d.dbq, d.dWk, d.dbk, d.dWv, d.dbv, d.dWo, d.dbo = grads
+    d.dWq, d.dbq, d.dWk, d.dbk, d.dWv, d.dbv, d.dWo, d.dbo = [G[n].data_ptr() for n in names]
     K.mha_bwd(d)
-    if defer:
-        dw = type(d).from_buffer_copy(d)
-        dw.dWq, dw.dbq, dw.dWk, dw.dbk, dw.dWv, dw.dbv, dw.dWo, dw.dbo = grads
-
-        def wgrad():
-            wsb = K._gemm_ws(dy.device)        # the aux stream's own split-K scratch
-            dw.gemm_ws, dw.gemm_ws_bytes = wsb.data_ptr(), wsb.numel()
-            K.mha_bwd_wgrad(dw)
-        # the branch reads x, o, dy and the scratch's dQ / dK / dV: referenced until the join
-        aux.run(wgrad, scratch, dyc, s["x"], s["o"])
     return dx
 
 
@@ -141,7 +111,7 @@ def sa_transformer_bwd(P, G, scope, s, dz, ws, aux=None):
     K.act_bwd(dz, s["u"], du, "tanh")
     dy = lin_bwd(s["y"], du, P[f"{scope}/transform/kernel"], G[f"{scope}/transform/kernel"],
                  G[f"{scope}/transform/bias"], ws, aux=aux)
-    dx = mha_bwd(P, G, f"{scope}/mha", s, dy, ws, aux=aux)
+    dx = mha_bwd(P, G, f"{scope}/mha", s, dy, ws)
     K.axpby(dz, dx, 1.0, 1.0)                                        # residual
     return dx
 
@@ -417,11 +387,6 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
     #      encoder BiLSTM BPTT holds 64 of them); model_backward joins the stream.  Everything the
     #      branch reads stays referenced until the join; it writes only its own gradient rows.
     aux_s = aux.s if aux is not None else torch.cuda.current_stream()
-    # the branch forks after the attention parameter pass is issued (so it waits for it: the
-    # pass, on the critical path, no longer shares the chip with these products; 14.86 -> 14.83
-    # ms/step, two rounds on one box); SAT_DEC_WGRAD_FORK=bptt forks it at the BPTT (A/B)
-    late = os.environ.get("SAT_DEC_WGRAD_FORK", "pg") == "pg"
-
     def fork_wgrad():
         if aux is not None:
             aux.s.wait_stream(torch.cuda.current_stream())
@@ -437,22 +402,11 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
         h1raw = S["H1RAW"].view(Tp * B, Dd)
         h1s = S["H1S"][:Tp].reshape(Tp * B, Dd)
         h0raw = S["H0RAW"].view(Tp * B, A)
-        if WGRAD_BATCH:
-            # (A/B only, WGRAD_BATCH above)
-            K.gemm_wgrad_batch([h1raw, h2s], DG2f, [dW2[:Dd], dW2[Dd:]],
-                               colsum=G["decoder/lstm2/bias"])
-            if A == Dd:
-                K.gemm_wgrad_batch([h1s, h0raw], DG1f, [dW1[h1_rows], dW1[:A]],
-                                   colsum=G["decoder/lstm1/bias"])
-            else:
-                K.gemm(h1s.t(), DG1f, dW1[h1_rows], beta=1.0, colsum=G["decoder/lstm1/bias"])
-                K.gemm(h0raw.t(), DG1f, dW1[:A], beta=1.0)
-        else:
-            K.gemm(h2s.t(), DG2f, dW2[Dd:], beta=1.0)
-            K.gemm(h1raw.t(), DG2f, dW2[:Dd], beta=1.0,
-                   colsum=G["decoder/lstm2/bias"])                 # + the bias gradient
-            K.gemm(h1s.t(), DG1f, dW1[h1_rows], beta=1.0, colsum=G["decoder/lstm1/bias"])
-            K.gemm(h0raw.t(), DG1f, dW1[:A], beta=1.0)
+        K.gemm(h2s.t(), DG2f, dW2[Dd:], beta=1.0)
+        K.gemm(h1raw.t(), DG2f, dW2[:Dd], beta=1.0,
+               colsum=G["decoder/lstm2/bias"])                 # + the bias gradient
+        K.gemm(h1s.t(), DG1f, dW1[h1_rows], beta=1.0, colsum=G["decoder/lstm1/bias"])
+        K.gemm(h0raw.t(), DG1f, dW1[:A], beta=1.0)
         ctx_all = S["REC0"][1:].reshape(Tp * B, R0)[:, :M1 + M2]
         K.gemm(ctx_all.t(), DG1f, dW1[A:A + M1 + M2], beta=1.0)
 
@@ -491,8 +445,6 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
             K.gemm(S["Q"].view(Tp * B, D1 + D2)[:, :D1].t(), DZf, dwk[M1:M1 + D1], beta=1.0,
                    colsum=G[f"{tf_}/bias"])
 
-    if not late:
-        fork_wgrad()
     # ---- attention parameters: one pass over all steps (sat_attn_param_grads), then a column
     #      sum of its per-workgroup partial rows
     F, KW = (d.loc_f, d.loc_k) if fwd else (0, 0)
@@ -512,8 +464,9 @@ def decoder_bwd(P, G, hp, d, dsv, dH2, masks, ws, attn_tile=32, pipe: Pipeline =
         loc=S["LOC"] if fwd else None, s_prev=S["S1"], s_tstride=S["S1"].stride(0),
         de1=DE1, de2=DE2, df=DFH if fwd else None, dK1=dK1s, dK2=dK2s, pg=PG, pg_stride=pgs,
         tsplit=ts)
-    if late:
-        fork_wgrad()
+    # the weight-gradient branch forks after the attention parameter pass is issued (so it waits
+    # for it: the pass, on the critical path, does not share the chip with these products)
+    fork_wgrad()
     if fwd:
         dsts = [G[f"{a1}/attention_variable"], G[f"{a1}/location_layer/kernel"].view(-1),
                 G[f"{a1}/location_conv/kernel"].view(-1), G[f"{a1}/location_conv/bias"]]
@@ -716,21 +669,15 @@ def encoder_bwd(P, G, hp, d, sv, dm1, dm2, lengths, masks, ws, aux: Aux = None):
     K.bn_bwd(dy.view(-1, C2), sv["p2_pre"].view(-1, C2), None, dp2.view(-1, C2), s2["mean"],
              s2["var"], s2["gamma"], G["encoder/cbhg/proj2/bn/gamma"],
              G["encoder/cbhg/proj2/bn/beta"], ws, training=training)
-    # the two projections' weight gradients run after the conv bank's weight gradient on its
-    # side stream instead of forking here, where they held the CUs the dX chain's short BN /
-    # max-pool launches wait for (a 96 us column-sum finish behind a 127 us GEMM):
-    # 14.03 -> 13.99 ms/step, 3 interleaved rounds (profiles/r05q_tail_ab.txt);
-    # SAT_PROJ_DW_BANK=0 forks them here again
-    proj_later = (aux is not None and bank_fused(d, inp)
-                  and os.environ.get("SAT_BANK_DW_SIDE", "1") == "1"
-                  and os.environ.get("SAT_PROJ_DW_BANK", "1") == "1")
-    # SAT_PROJ_DW_SIDE2=1: those two products on a third side stream forked with the bank's
-    # (beside the bank dX and dW products) instead of queued behind the bank dW
-    proj_side2 = proj_later and os.environ.get("SAT_PROJ_DW_SIDE2", "0") == "1"
+    # with the fused conv bank and an aux stream, the two projections' weight gradients run after
+    # the conv bank's weight gradient on its side stream instead of forking here, where they
+    # held the CUs the dX chain's short BN / max-pool launches wait for (a 96 us column-sum finish
+    # behind a 127 us GEMM)
+    side = aux is not None and bank_fused(d, inp)
     later = []
 
     def proj_wgrad(fn, *tensors):
-        if proj_later:
+        if side:
             later.append(fn)
             aux.keep.extend(tensors)
         else:
@@ -763,34 +710,23 @@ def encoder_bwd(P, G, hp, d, sv, dm1, dm2, lengths, masks, ws, aux: Aux = None):
              _contig_span(G, [f"{n}/bn/gamma" for n in names]),
              _contig_span(G, [f"{n}/bn/beta" for n in names]), ws, training=training)
     # the conv bank's bias sum rides with its weight gradient on the side stream (it is 0.1 ms
-    # of the dX chain otherwise): 14.50 -> 14.48 ms/step, 5 of 5 interleaved pairs; the proj1 /
-    # proj2 weight gradients moved there too measured no further gain
+    # of the dX chain otherwise)
     bank_bias = lambda: K.colsum(dbank_pre.view(-1, KC),  # noqa: E731
                                  _contig_span(G, [f"{n}/bias" for n in names]), ws)
-    bias_side = (bank_fused(d, inp) and aux is not None
-                 and os.environ.get("SAT_BANK_DW_SIDE", "1") == "1"
-                 and os.environ.get("SAT_BANK_BIAS_SIDE", "1") == "1")
-    if not bias_side:
+    if not side:
         bank_bias()
     if bank_fused(d, inp):
         kern = [f"{n}/kernel" for n in names]
-        # the weight-gradient branch forks BEFORE the dX product is issued: a branch waits for
-        # everything the main stream has issued at its fork, so the other order serialises them
-        # the weight-gradient product on a stream of its own (not behind the aux backlog): the
-        # graph then runs it beside the dX product instead of before it on the same queue
-        # (14.52 -> 14.47 ms/step, 6 interleaved pairs; SAT_BANK_DW_SIDE=0 restores the aux branch)
         bank_dw = lambda: K.conv_bank_bwd(inp, _contig_span(P, kern), dbank_pre,  # noqa: E731
                                           d.max_k, C, dW=_contig_span(G, kern), beta_dw=1.0)
-        if aux is not None and os.environ.get("SAT_BANK_DW_SIDE", "1") == "1":
-            side = (lambda: (bank_bias(), bank_dw())) if bias_side else bank_dw
-            if proj_side2 and later:
-                aux.run_side(side, inp, dbank_pre)
-                aux.run_side(lambda: [f() for f in later], which=3)
-            else:
-                aux.run_side((lambda: (side(), [f() for f in later])) if later else side,
-                             inp, dbank_pre)
+        # the weight-gradient branch forks BEFORE the dX product is issued (a branch waits for
+        # everything the main stream has issued at its fork, so the other order serialises them),
+        # on a stream of its own, not behind the aux backlog: the graph then runs it beside the dX
+        # product instead of before it on the same queue
+        if side:
+            aux.run_side(lambda: (bank_bias(), bank_dw(), [f() for f in later]), inp, dbank_pre)
         else:
-            _wgrad(aux, bank_dw, inp, dbank_pre)
+            bank_dw()
         K.conv_bank_bwd(inp, _contig_span(P, kern), dbank_pre, d.max_k, C, dx=dinp,
                         beta_dx=1.0)
     else:
@@ -833,8 +769,6 @@ def model_backward(P, G, hp, d, sv, ws, attn_tile=32, pipe: Pipeline = SEQUENTIA
     if on_decoder_grads is not None:
         on_decoder_grads([torch.cuda.current_stream()] + (list(aux.used) if aux is not None
                                                           else []))
-    if aux is not None and os.environ.get("SAT_AUX2") == "1":
-        aux.switch()      # A/B: the encoder's weight-gradient branches on their own stream
     encoder_bwd(P, G, hp, d, sv, dm1, dm2, lengths, masks, ws, aux=aux)
     if aux is not None:
         aux.join()                                    # every weight-gradient branch

@@ -19,11 +19,10 @@
 //   record B_t = {tile statistics (m1, z1, a1, m2, z2), unnormalised partial contexts (288),
 //                 the tile's first 5 / last 4 energies and last 2 alignments (the halos the
 //                 neighbours' location convolution and alignment recursion need)}.
-// Iteration t:  [B_{t-1}: combine c_{t-1}] -> LSTM step t (h part of the dot done at the end of
-// iteration t-1) -> publish A_t -> [normalise s_{t-1}, alpha_{t-1} on the own positions,
-// location features, query-independent part of the energies -- all in the shadow of A_t's
-// latency] -> [A_t: q_t, h_t] -> energies, tile statistics, partial contexts -> publish B_t ->
-// h part of step t+1's gate sums.
+// Iteration t:  [B_{t-1}: combine c_{t-1}] -> LSTM step t (h and c parts in one dot) ->
+// publish A_t -> [normalise s_{t-1}, alpha_{t-1} on the own positions, location features,
+// query-independent part of the energies -- all in the shadow of A_t's latency] ->
+// [A_t: q_t, h_t] -> energies, tile statistics, partial contexts -> publish B_t.
 // Consistency rule: every value that crosses a workgroup boundary is tagged when it is made and
 // its maker uses the tagged value too, so all readers (and the histories) see identical bits.
 // Every spin is bounded (persistent.h poll_give_up): a timeout raises err[0], later polls give
@@ -34,60 +33,6 @@
 #ifndef SAT_FWD8_TRACE
 #define SAT_FWD8_TRACE 0
 #endif
-#ifndef SAT_FWD8_NORM3
-#define SAT_FWD8_NORM3 1     // the normalise window's history stores on wave 7 (A/B switch)
-#endif
-#ifndef SAT_FWD8_HSTORE7
-#define SAT_FWD8_HSTORE7 1   // the cell's C0 / REC0 / H0RAW / G0 stores on wave 7 (A/B switch)
-#endif
-#ifndef SAT_FWD8_ESCALE
-// the energies' tanh argument pre-scaled: K + b1 + convb W_loc and the folded location weights
-// held x 2 log2(e) in LDS, so tanh(a + q) = 1 - 2 / (1 + exp2(fma(q, 2 log2 e, a'))) takes one
-// fma where the plain form took an add and a multiply (16 per lane per step): 5.65 -> 5.58 us
-// per step over three interleaved rounds on one box (profiles/r05_fwd8_ab.txt)
-#define SAT_FWD8_ESCALE 1
-#endif
-#ifndef SAT_FWD8_POLL1
-// the hand-off polls' first attempt branch-free: every lane issues its loads (clamped in-record
-// addresses for lanes without one), the tags are checked, and only a miss enters the retry
-// loop -- the first attempt succeeds on the critical path (trace: 0 spins), where the loop's
-// per-load exec-mask branches were ~30 branches + 150 scalar instructions of the staging phase
-#define SAT_FWD8_POLL1 1
-#endif
-#ifndef SAT_FWD8_HMERGE
-// the h part of the gate sums inside the cell phase's dot (one dot, one transpose-reduce) rather
-// than a separate h-dot after publishing record B: 5.84 -> 5.78 us/step (three interleaved
-// rounds on one box).  The separate h-dot was meant to hide in B's latency, but the group's
-// last publisher (whichever workgroup it is) never waits -- every other record is already
-// there when it polls -- so its h-dot sat on the group's period (0: the old placement, A/B)
-#define SAT_FWD8_HMERGE 1
-#endif
-
-#ifndef SAT_FWD8_R1
-// the S1 / S2 / ST history stores of step t-1 on wave 7 in the location-term window (where it
-// holds no positions and idles until record A_t arrives) instead of the combine window, where
-// the trace showed wave 7 finishing last (1.51 vs <= 1.39 us into the step): with R2,
-// 5.16 -> 5.10 us/step (two A/B rounds on one box, profiles/r06i_fwd8_rebalance_ab.txt)
-#define SAT_FWD8_R1 1
-#endif
-#ifndef SAT_FWD8_R2
-// record B's halo words published by wave 7 at the start of the statistics phase (the energies
-// and alpha_{t-1} are final there) instead of by wave 1 after its contexts: wave 1, which also
-// publishes the statistics, was the group's last B publisher in the trace: with R1,
-// 5.21 -> 5.10 us/step
-#define SAT_FWD8_R2 1
-#endif
-#ifndef SAT_FWD8_STW
-#define SAT_FWD8_STW 1   // the wave that sums and publishes record B's statistics words
-#endif
-#ifndef SAT_FWD8_R4
-#define SAT_FWD8_R4 0    // A/B: the AL1 history store on wave 7 in the location window
-#endif
-#ifndef SAT_FWD8_C2W
-// the wave that forms the 32 c2 partial contexts besides its own c1 columns (A/B: wave 3, the
-// trace's earliest B publisher, measured 5.10 -> 5.14 us/step against wave 0)
-#define SAT_FWD8_C2W 0
-#endif
 
 namespace sat {
 namespace {
@@ -95,6 +40,8 @@ namespace {
 constexpr int kW = 8;                  // workgroups per utterance
 constexpr int kGmax = 32;              // utterances (groups); grid = 256
 constexpr int kTh = 512;               // threads: 8 waves, 2 per SIMD (256 registers each)
+constexpr int kStW = 1;                // wave that sums and publishes record B's statistics words
+constexpr int kC2W = 0;                // wave that forms the 32 c2 partial contexts besides its c1
 constexpr int kU = 256, kM1 = 256, kM2 = 32, kD1 = 224, kD2 = 32, kF = 5, kKW = 10;
 constexpr int kC = kM1 + kM2;          // 288 context dims
 constexpr int kK0 = kC + kU;           // 544 inputs of the attention RNN's recurrent product
@@ -172,7 +119,6 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
   __shared__ __attribute__((aligned(16))) float hraw[kUW];       // own units' raw outputs
   __shared__ float cown[kUW];                                    // own units' c_t
   __shared__ __attribute__((aligned(16))) float4 gown[kUW];      // own units' gates (i, j, f, o)
-  __shared__ float gsum[8][64];             // h part of the gate sums (transpose-reduced)
   __shared__ float halo[12];                // e_{t-1} left 4 | right 5 ; alpha_{t-2} at n0-2, n0-1
   __shared__ float eown[kPmax], e2own[kPmax];
   __shared__ float alf[2][kPmax + 1];       // alf[t & 1][k] = alpha_{t-1} at n0 - 1 + k
@@ -189,7 +135,7 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
   const bool has_left = j > 0, has_right = j + 1 < kW && n0 + P < N;
   // wave 7 holds no energy positions when nt <= 28: it then stores the cell's histories in the
   // location-term phase (from LDS) instead of the cell lanes of every wave
-  const bool w7_stores = SAT_FWD8_HSTORE7 && 4 * 7 >= nt;
+  const bool w7_stores = 4 * 7 >= nt;
   const int64_t bN = (int64_t)b * N;
   const int len = (int)p.lengths[b];
   const float u = p.u;
@@ -233,7 +179,7 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
     }
     const float kv = r >= nt ? 0.f : c < kD1 ? p.K1[(bN + n0 + r) * kD1 + c] + p.b1[c] + lb
                                             : p.K2[(bN + n0 + r) * kD2 + (c - kD1)];
-    kc[r][c] = SAT_FWD8_ESCALE ? kv * kTwoLog2e : kv;
+    kc[r][c] = kv * kTwoLog2e;
   }
   for (int i = tid0; i < kKW * kQ; i += kTh) {
     const int k = i / kQ, c = i - k * kQ;
@@ -242,7 +188,7 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
 #pragma unroll
       for (int f = 0; f < kF; ++f) a = fmaf(p.convW[k * kF + f], p.locW[f * kD1 + c], a);
     }
-    cwl[k][c] = SAT_FWD8_ESCALE ? a * kTwoLog2e : a;
+    cwl[k][c] = a * kTwoLog2e;
   }
   for (int i = tid0; i < kPmax * kM1 / 4; i += kTh) {
     const int r = i / (kM1 / 4), c4 = i - r * (kM1 / 4);
@@ -258,7 +204,6 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
   if (tid0 < kF) cw[kKW * kF + tid0] = p.convb[tid0];
   if (tid0 < kU) hbuf[tid0] = 0.f;                                  // h_{-1}
   if (tid0 < 16) tp[tid0] = 0;
-  gsum[tid0 >> 6][tid0 & 63] = 0.f;          // h_{-1} = 0: no h part at step 0
   // initial state rows (host): s_{-1} on the conv window, alpha_{-1} on n0-1 .. n0+nt-1
   // (tagged with step 0's bit: they travel in record B_0)
   if (tid0 < nt + kKW - 1) {
@@ -406,18 +351,18 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       const long long tq1 = wall_clock64();
 #endif
-      bool retry = true;
-      if (SAT_FWD8_POLL1) {
-        x1 = ldc4(rRB, (rec + kRBctx) / 4 + lane);
-        x2 = ldc4(rRB, i2);                    // (lanes >= 10: in-record words, unused)
-        const float h0 = ldc(rRB, hsrc ? hw : 0);
-        hv = hsrc ? h0 : 0.f;                  // an absent neighbour's halo words stay 0
-        ok1 = tag_ok4(x1, want);
-        ok2 = ok2 || tag_ok4(x2, want);
-        ok3 = ok3 || tag_ok(hv, want);
-        retry = any_lane(!(ok1 && ok2 && ok3)) && !gave_up;
-      }
-      if (retry) {
+      // first attempt branch-free: every lane issues its loads (clamped in-record addresses for
+      // lanes without one) and only a miss enters the retry loop -- the first attempt succeeds on
+      // the critical path (trace: 0 spins), where the loop's per-load exec-mask branches cost
+      // ~30 branches + 150 scalar instructions of the staging phase
+      x1 = ldc4(rRB, (rec + kRBctx) / 4 + lane);
+      x2 = ldc4(rRB, i2);                    // (lanes >= 10: in-record words, unused)
+      const float h0 = ldc(rRB, hsrc ? hw : 0);
+      hv = hsrc ? h0 : 0.f;                  // an absent neighbour's halo words stay 0
+      ok1 = tag_ok4(x1, want);
+      ok2 = ok2 || tag_ok4(x2, want);
+      ok3 = ok3 || tag_ok(hv, want);
+      if (any_lane(!(ok1 && ok2 && ok3)) && !gave_up) {
         for (unsigned spins = 0;; ++spins) {
           if (!ok1) x1 = ldc4(rRB, (rec + kRBctx) / 4 + lane);
           if (!ok2) x2 = ldc4(rRB, i2);
@@ -487,8 +432,6 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
               const float e = e_at(n0 - kPadL + lane);
               const float sv = e == -INFINITY ? 0.f : __expf(e - M1) * __builtin_amdgcn_rcpf(Z1);
               sp[lane] = sv;
-              if (!SAT_FWD8_NORM3 && lane >= kPadL && lane < nt + kPadL)
-                p.S1[((int64_t)t * B + b) * N + n0 + lane - kPadL] = sv;
             }
             if (t < T && 4 * 7 < nt) {         // no idle energy wave (N > 224): here
               asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -509,31 +452,18 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
               }
               const float at = tagf(av, bit);
               alf[t & 1][k] = at;
-              if (k >= 1 && !(SAT_FWD8_R4 && w7_stores && t < T))
+              if (k >= 1)
                 p.AL1[((int64_t)t * B + b) * N + n] = at;
             }
           }
           // wave 7 (idle in this window): the S1 / S2 / ST history stores (S1 recomputed with
           // wave 5's arithmetic: the same bits), off waves 5 and 6 whose LDS results the next
           // phases wait for
-          // (deferred to wave 7's location-term window when it idles there, SAT_FWD8_R1; the
+          // (deferred to wave 7's location-term window when it idles there -- in the combine
+          // window the trace showed wave 7 finishing last, 1.51 vs <= 1.39 us into the step; the
           // last step's here)
-          const bool defer = SAT_FWD8_R1 && w7_stores && t < T;
-          if (SAT_FWD8_NORM3 ? (wave == 7 && !defer) : wave == 6) {
-            if (SAT_FWD8_NORM3) {
-              store_hist(t, lane, M1, Z1, A1, M2, Z2);
-            } else {
-              if (lane < nt) {
-                const float e2 = e2own[lane];
-                p.S2[((int64_t)s * B + b) * N + n0 + lane] =
-                    e2 == -INFINITY ? 0.f : __expf(e2 - M2) * __builtin_amdgcn_rcpf(Z2);
-              }
-              if (j == 0 && lane == 0) {
-                float* stp = p.ST + ((int64_t)s * B + b) * 4;
-                stp[0] = M1; stp[1] = Z1; stp[2] = A1 / Z1; stp[3] = Z2;
-              }
-            }
-          }
+          const bool defer = w7_stores && t < T;
+          if (wave == 7 && !defer) store_hist(t, lane, M1, Z1, A1, M2, Z2);
         }
       }
     }
@@ -550,8 +480,9 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) acc[q] = f2{0.f, 0.f};
       if (t > 0) {
-#if SAT_FWD8_HMERGE
-        // h_{t-1} (staged with records A_{t-1}) and c_{t-1} in ONE dot and ONE transpose-reduce
+        // h_{t-1} (staged with records A_{t-1}) and c_{t-1} in ONE dot and ONE transpose-reduce: a
+        // separate h-dot after publishing record B sat on the group's period, because the
+        // group's last publisher never waits for B
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float xv = hbuf[64 * i + lane];
@@ -559,7 +490,6 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
 #pragma unroll
           for (int q = 0; q < 8; ++q) acc[q] = __builtin_elementwise_fma(xx, w0[i][q], acc[q]);
         }
-#endif
 #pragma unroll
         for (int i = 4; i < 8; ++i) {
           const float xv = cbuf[64 * (i - 4) + lane];
@@ -587,11 +517,7 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
       // lane holds column m = lane >> 2: activation of its gate (i, f, o sigmoid; j tanh via
       // 2 sigm(2x) - 1; forget_bias 1.0), then the cell lane (16q) gathers its unit's 4 gates
       const int gate = (lane >> 2) & 3;
-#if SAT_FWD8_HMERGE
       const float pre = v[0] + xgn;
-#else
-      const float pre = v[0] + gsum[wave][lane] + xgn;
-#endif
       const float sg = sigm_fast(gate == 1 ? 2.f * pre : pre + (gate == 2 ? 1.0f : 0.f));
       const float act = gate == 1 ? fmaf(2.f, sg, -1.f) : sg;
       const float gj = dpp_mov<0x104>(act);        // row_shl:4, 8, 12
@@ -660,11 +586,8 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
     //                 10-tap product (modules/forward_attention.py:98-101)
     // energy role: lane = dim chunk c (4 dims of [D1 | D2]), wave = positions 4w .. 4w+3
     float4 Lr[4];
-    if (SAT_FWD8_R1 && SAT_FWD8_NORM3 && w7_stores && wave == 7 && t > 0)
+    if (w7_stores && wave == 7 && t > 0)
       store_hist(t, lane, M1, Z1, A1, M2, Z2);   // wave 7 holds no positions: idle here
-    if (SAT_FWD8_R4 && w7_stores && wave == 7 && t > 0 && lane >= 1 && lane <= nt &&
-        n0 - 1 + lane >= 0)
-      p.AL1[((int64_t)t * B + b) * N + n0 - 1 + lane] = alf[t & 1][lane];   // alpha_{t-1}
     if (4 * wave < nt) {
       const int c = lane;
 #pragma unroll
@@ -695,15 +618,11 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       const long long tq1 = wall_clock64();
 #endif
-      bool retry = true;
-      if (SAT_FWD8_POLL1) {
-        x1 = ldc4(rRA, ra / 4 + lane);
-        x2 = ldc4(rRA, (ra + kQ) / 4 + (two ? lane : 0));
-        ok1 = tag_ok4(x1, want);
-        ok2 = ok2 || tag_ok4(x2, want);
-        retry = any_lane(!(ok1 && ok2)) && !gave_up;
-      }
-      if (retry) {
+      x1 = ldc4(rRA, ra / 4 + lane);         // first attempt branch-free, as for records B
+      x2 = ldc4(rRA, (ra + kQ) / 4 + (two ? lane : 0));
+      ok1 = tag_ok4(x1, want);
+      ok2 = ok2 || tag_ok4(x2, want);
+      if (any_lane(!(ok1 && ok2)) && !gave_up) {
         for (unsigned spins = 0;; ++spins) {
           if (!ok1) x1 = ldc4(rRA, ra / 4 + lane);
           if (!ok2) x2 = ldc4(rRA, (ra + kQ) / 4 + lane);
@@ -747,16 +666,13 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r = 4 * wave + i;
-#if SAT_FWD8_ESCALE
+        // kc and cwl hold their terms x 2 log2(e), so the exp2 argument takes one fma where the
+        // plain tanh(a + q) took an add and a multiply (16 per lane per step)
         auto tz = [](float a2, float qv) {        // tanh(a + q) from a' = 2 log2(e) a
           return fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(fmaf(qv, kTwoLog2e, a2))), 1.f);
         };
         const float4 z = make_float4(tz(Lr[i].x, q.x), tz(Lr[i].y, q.y), tz(Lr[i].z, q.z),
                                      tz(Lr[i].w, q.w));
-#else
-        const float4 z = make_float4(tanh_fast(Lr[i].x + q.x), tanh_fast(Lr[i].y + q.y),
-                                     tanh_fast(Lr[i].z + q.z), tanh_fast(Lr[i].w + q.w));
-#endif
         float a = v4.x * z.x;
         a = fmaf(v4.y, z.y, a); a = fmaf(v4.z, z.z, a); a = fmaf(v4.w, z.w, a);
         e[i] = d1 ? a : 0.f;
@@ -804,13 +720,14 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
     tick(12);
     ev(13);
     // tile statistics (every wave redundantly, lane = position) and the wave's own copy of
-    // the alignment weights; wave 1 publishes the statistics words
+    // the alignment weights; wave kStW publishes the statistics words
     {
       const unsigned bit = lsb_tag(t);
       const float* al = alf[t & 1];            // alpha_{t-1} at n0-1+k
-      if (SAT_FWD8_R2 && wave == 7 && lane < kPadR + kPadL + 2) {
+      if (wave == 7 && lane < kPadR + kPadL + 2) {
         // record B's halo words (first 5 / last 4 energies, last 2 alpha_{t-1}): final since the
-        // energies barrier
+        // energies barrier (wave 7 rather than wave 1 after its contexts: wave 1, which also
+        // publishes the statistics, was the group's last B publisher in the trace)
         const int rb = (((t & 1) * B + b) * kW + j) * kRB;
         const int q = lane;
         float v;
@@ -827,7 +744,7 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
       const float pe2 = e2v == -INFINITY ? 0.f : __expf(e2v - m2);
       const float w = lane < nt ? ((1.f - u) * al[lane + 1] + u * al[lane] + 1e-7f) * pe : 0.f;
       if (lane < kPmax) { wsc[wave][0][lane] = w; wsc[wave][1][lane] = lane < nt ? pe2 : 0.f; }
-      if (wave == SAT_FWD8_STW) {
+      if (wave == kStW) {
         const float z1 = tagf(wave_sum_dpp(pe), bit), a1 = tagf(wave_sum_dpp(w), bit);
         const float z2 = tagf(wave_sum_dpp(pe2), bit);
         if (lane == 0) {
@@ -841,8 +758,7 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
     tick(13);
     ev(14);
     // partial contexts, published per wave: wave w owns c1 columns 32w .. 32w+31 (lane l:
-    // column 32w + (l & 31), positions 16 (l >> 5) .. + 15); wave SAT_FWD8_C2W also the 32 c2
-    // columns; wave 1 the halo words unless SAT_FWD8_R2 (then wave 7 in the statistics phase)
+    // column 32w + (l & 31), positions 16 (l >> 5) .. + 15); wave kC2W also the 32 c2 columns
     {
       const unsigned bit = lsb_tag(t);
       const int rb = (((t & 1) * B + b) * kW + j) * kRB;
@@ -860,43 +776,18 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
       const float4 c4 = quad_gather(fold32(c));
       if (lane < 32 && (lane & 3) == 0)
         stc4x(xl, rRB, (rb + kRBctx) / 4 + 8 * wave + (lane >> 2), tagf4(c4, bit));
-      if (wave == SAT_FWD8_C2W) {
-        const float* ws2 = &wsc[SAT_FWD8_C2W][1][r0];
+      if (wave == kC2W) {
+        const float* ws2 = &wsc[kC2W][1][r0];
         float c2 = 0.f;
 #pragma unroll
         for (int k = 0; k < 16; ++k) c2 = fmaf(ws2[k], v2s[r0 + k][col], c2);
         const float4 q4 = quad_gather(fold32(c2));
         if (lane < 32 && (lane & 3) == 0)
           stc4x(xl, rRB, (rb + kRBctx + kM1) / 4 + (lane >> 2), tagf4(q4, bit));
-      } else if (!SAT_FWD8_R2 && wave == 1 && lane < kPadR + kPadL + 2) {
-        const int q = lane;
-        float v;
-        if (q < kPadR) v = q < nt ? eown[q] : -INFINITY;
-        else if (q < kPadR + kPadL) { const int i = nt - kPadL + (q - kPadR); v = i >= 0 ? eown[i] : -INFINITY; }
-        else { const int k = nt - 1 + (q - kPadR - kPadL); v = k >= 0 ? alf[t & 1][k] : 0.f; }
-        stcx(xl, rRB, rb + kRBeh + q, tagf(v == -INFINITY ? 0.f : v, bit));
       }
     }
     tick(14);
     ev(15);
-    // ============ 7. h part of step t+1's gate sums (h_t arrived with records A_t)
-    if (!SAT_FWD8_HMERGE && t + 1 < T) {
-      f2 acc[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] = f2{0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float xv = hbuf[64 * i + lane];
-        const f2 xx = {xv, xv};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc[q] = __builtin_elementwise_fma(xx, w0[i][q], acc[q]);
-      }
-      float v[16];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) { v[2 * q] = acc[q].x; v[2 * q + 1] = acc[q].y; }
-      transpose_reduce16(v, lane);
-      gsum[wave][lane] = v[0];                    // own wave's slot: no barrier needed
-    }
     tick(15);
   }
 #if SAT_FWD8_TRACE || SAT_SEGMENT_CLOCKS

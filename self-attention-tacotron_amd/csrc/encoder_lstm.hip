@@ -21,21 +21,10 @@ namespace {
 constexpr int kU = 128;            // units per direction
 constexpr int kG4 = 4 * kU;        // gate columns (512)
 constexpr int kTh = 1024;
-// BPTT workgroup: SAT_ENC_BWD8 (default) 8 waves, each 16 units x 8 gate columns per lane (128
-// weights); otherwise 16 waves of 8 units x 8 columns.  The step is issue-bound: the 16-wave
-// form spent ~3/4 of its instructions on per-wave overhead (the cell on 8 of 64 lanes, the
-// 64-lane reduce, addresses) that every wave repeats.
-#ifndef SAT_ENC_BWD8
-#define SAT_ENC_BWD8 1
-#endif
-// SAT_ENC_BWD_DMA: the cell operands (G, c_{t-1}, dL/dh, zoneout masks: 4 KB per step) stream
-// into LDS by asm LDS-DMA a chunk of 8 steps ahead (wave w loads step w of the next chunk,
-// double-buffered), waited for once per chunk; the per-step register prefetch exposed its
-// load latency (no operand loads at all: 229 -> 148 us, profiles/r06z_enc_bwd_dma_ab.txt)
-#ifndef SAT_ENC_BWD_DMA
-#define SAT_ENC_BWD_DMA 1
-#endif
-constexpr int kRowsB = SAT_ENC_BWD8 ? 16 : 8;      // units per wave
+// BPTT workgroup: 8 waves, each 16 units x 8 gate columns per lane (128 weights).  The step is
+// issue-bound: a 16-wave form (8 units per wave) spent ~3/4 of its instructions on per-wave
+// overhead (the cell on 8 of 64 lanes, the 64-lane reduce, addresses) that every wave repeats.
+constexpr int kRowsB = 16;         // units per wave
 constexpr int kThB = 64 * (kU / kRowsB);
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -60,29 +49,19 @@ struct EncBwdP {
   float* DG[2];
 };
 
-// Forward.  Dot role (SAT_ENC_FWD_T, default): thread t owns gate columns 4cb .. 4cb+3
+// Forward.  Dot role: thread t owns gate columns 4cb .. 4cb+3
 // (cb = t >> 3) over recurrent rows 16rg .. 16rg+15 (rg = t & 7): 64 weights in registers, 16
 // state values read from LDS per step (4 ds_read_b128; the former layout -- one column, 64
 // rows per thread -- read 64, and 1024 threads x 256 B of LDS reads per step bound the step at
 // the LDS data path); the 8 row groups' partial sums of the 4 columns meet by a DPP
 // transpose-reduce, after which lanes 2m of each 8-lane group hold column 4cb + m.
 // Cell role: threads u < 128 own unit u's (c, h) state in registers.
-// SAT_ENC_DRAIN_CELL: wait for the step's operand prefetch right before the cell (whose stores
-// then stay in flight into the next step) instead of at the loop's back edge, where the
-// compiler's vmcnt(0) also waits for the cell's stores
-#ifndef SAT_ENC_DRAIN_CELL
-#define SAT_ENC_DRAIN_CELL 1
-#endif
-#ifndef SAT_ENC_FWD_T
-#define SAT_ENC_FWD_T 1
-#endif
 __global__ void __launch_bounds__(kTh) enc_lstm_fwd_kernel(EncFwdP p) {
   __shared__ __attribute__((aligned(16))) float hs[kU];
   __shared__ __attribute__((aligned(16))) float gp[kG4];
   const int tid = threadIdx.x;
   const int d = blockIdx.x & 1, b = blockIdx.x >> 1;
   const int N = p.N, B = p.B;
-#if SAT_ENC_FWD_T
   const int lane = tid & 63;
   const int cb = tid >> 3, rg = tid & 7;
   const int c = 4 * cb + 2 * ((lane >> 2) & 1) + ((lane >> 1) & 1);   // column after the reduce
@@ -98,16 +77,6 @@ __global__ void __launch_bounds__(kTh) enc_lstm_fwd_kernel(EncFwdP p) {
         w[r][cp] = f2{src[0], src[1]};
       }
   }
-#else
-  const int c = tid >> 1, hf = tid & 1;
-  f2 w[32];
-  {
-    const float* W = p.W[d];
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-      w[i] = f2{W[(int64_t)(64 * hf + 2 * i) * kG4 + c], W[(int64_t)(64 * hf + 2 * i + 1) * kG4 + c]};
-  }
-#endif
   const int len = (int)p.lengths[b];
   const bool cell = tid < kU;
   const int u = tid;
@@ -148,7 +117,6 @@ __global__ void __launch_bounds__(kTh) enc_lstm_fwd_kernel(EncFwdP p) {
     const float xv = xn, mc = mcn, mh = mhn;
     xn = load_x(i + 1);
     load_m(i + 1, mcn, mhn);
-#if SAT_ENC_FWD_T
     {
       const float4* h4 = reinterpret_cast<const float4*>(&hs[16 * rg]);
       f2 a0 = {0.f, 0.f}, a1 = {0.f, 0.f}, b0 = {0.f, 0.f}, b1 = {0.f, 0.f};
@@ -171,27 +139,11 @@ __global__ void __launch_bounds__(kTh) enc_lstm_fwd_kernel(EncFwdP p) {
       v[0] += dpp_mov<0xB1>(v[0]);         // lane bit 0: the last pair of row groups
       if (!hf) gp[c] = v[0] + xv;
     }
-#else
-    // ---- gate pre-activations: column c, rows 64 hf .. 64 hf + 63
-    {
-      const float4* h4 = reinterpret_cast<const float4*>(&hs[64 * hf]);
-      f2 a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const float4 h = h4[q];
-        a0 = __builtin_elementwise_fma(f2{h.x, h.y}, w[2 * q], a0);
-        a1 = __builtin_elementwise_fma(f2{h.z, h.w}, w[2 * q + 1], a1);
-      }
-      float acc = (a0.x + a0.y) + (a1.x + a1.y);
-      acc += dpp<0xB1>(acc);                // the pair (lanes t, t ^ 1) of column c
-      if (hf == 0) gp[c] = acc + xv;
-    }
-#endif
     // LDS-only barriers: a __syncthreads would also drain the prefetch and the history stores
     lds_barrier();
-#if SAT_ENC_DRAIN_CELL
-    vm_drain();   // this step's operand prefetch landed; the cell's stores then stay in flight
-#endif
+    // this step's operand prefetch landed; the cell's stores then stay in flight into the next
+    // step (at the loop's back edge the compiler's vmcnt(0) would also wait for those stores)
+    vm_drain();
     // ---- cell
     if (cell) {
       const float4 g = *reinterpret_cast<const float4*>(&gp[4 * u]);
@@ -222,18 +174,15 @@ __global__ void __launch_bounds__(kTh) enc_lstm_fwd_kernel(EncFwdP p) {
 }
 
 // Backward.  Recurrent product, wave-transposed: wave w owns rows R w .. R w + R-1 (units; R =
-// kRowsB, 16 in the 8-wave form), lane l gate columns 8l .. 8l+7 of them (8R weights in
-// registers), so a step reads 8 floats of the previous step's gate gradients per lane; the R
+// kRowsB), lane l gate columns 8l .. 8l+7 of them (8R weights in registers), so a step reads 8 floats of the previous step's gate gradients per lane; the R
 // partial row sums are transpose-reduced across the wave and lane (64/R) m runs unit R w + m's
 // reverse step with its carries in registers.  The gate gradients of the previously processed
 // step sit in LDS (double buffer: one barrier per step).
 __global__ void __launch_bounds__(kThB) enc_lstm_bwd_kernel(EncBwdP p) {
   __shared__ __attribute__((aligned(16))) float dgn[2][kG4];
-#if SAT_ENC_BWD_DMA
   static_assert(kThB == 512, "one wave per step of an 8-step chunk");
   // [buffer][step of the chunk][G 4U | c_{t-1} U | dL/dh U | mask c U | mask h U]
   __shared__ __attribute__((aligned(16))) float opsb[2][8][8 * kU];
-#endif
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int d = blockIdx.x & 1, b = blockIdx.x >> 1;
   const int N = p.N, B = p.B;
@@ -255,29 +204,10 @@ __global__ void __launch_bounds__(kThB) enc_lstm_bwd_kernel(EncBwdP p) {
   const int u = kRowsB * wave + lane / kLPU;
   const bool masked = p.mc[0] != nullptr;
   struct Ops { float4 g; float cp, dy, mc, mh; };
-  auto load_ops = [&](int i) {
-    Ops o{make_float4(0.f, 0.f, 0.f, 0.f), 0.f, 0.f, 1.f - p.zc, 1.f - p.zh};
-#if SAT_ENC_PROBE_NOLOAD
-    if (i >= 0) return o;   // timing probe only: no operand loads (wrong results)
-#endif
-    if (lead && i < N) {
-      const int n = d ? i : N - 1 - i;
-      const int cprow = d ? n + 1 : n;      // c_{t-1} in processing order of the direction
-      const int64_t bu = (int64_t)b * kU + u;
-      o.g = reinterpret_cast<const float4*>(p.G[d])[(int64_t)n * B * kU + bu];
-      o.cp = p.CS[d][(int64_t)cprow * B * kU + bu];
-      o.dy = p.DY[(int64_t)b * p.dy_sb + (int64_t)n * p.dy_sn + d * kU + u];
-      if (masked) {
-        const int64_t r = ((int64_t)n * B + b) * kU + u;
-        o.mc = p.mc[d][r];
-        o.mh = p.mh[d][r];
-      }
-    }
-    return o;
-  };
-#if SAT_ENC_BWD_DMA
-  (void)load_ops;   // the register path of SAT_ENC_BWD_DMA=0
-  // step ii's operands (clamped to a valid step past N: loaded, never used) into opsb[buf][w]
+  // The cell operands (G, c_{t-1}, dL/dh, zoneout masks: 4 KB per step) stream into LDS by asm
+  // LDS-DMA a chunk of 8 steps ahead (wave w loads step w of the next chunk, double-buffered),
+  // waited for once per chunk; a per-step register prefetch exposed its load latency.
+  // dma_step: step ii's operands (clamped to a valid step past N: loaded, never used) into opsb[buf][w]
   auto dma_step = [&](int ii, int buf) {
     const int ic = min(ii, N - 1);
     const int n = d ? ic : N - 1 - ic;
@@ -298,18 +228,11 @@ __global__ void __launch_bounds__(kThB) enc_lstm_bwd_kernel(EncBwdP p) {
   };
   dma_step(wave, 0);                       // chunk 0
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#elif SAT_ENC_BWD_PF2
-  // operands prefetched two steps ahead (one step ahead, their load latency showed in the step)
-  Ops nxt = load_ops(0), nxt2 = load_ops(1);
-#else
-  Ops nxt = load_ops(0);
-#endif
   float dh_c = 0.f, dc_c = 0.f;
   vm_drain();                              // (see the forward: weights landed before the loop)
   __syncthreads();
   for (int i = 0; i < N; ++i) {
     const int n = d ? i : N - 1 - i;
-#if SAT_ENC_BWD_DMA
     if ((i & 7) == 0) dma_step(i + 8 + wave, ((i >> 3) + 1) & 1);   // the next chunk
     Ops o{make_float4(0.f, 0.f, 0.f, 0.f), 0.f, 0.f, 1.f - p.zc, 1.f - p.zh};
     if (lead) {
@@ -322,15 +245,6 @@ __global__ void __launch_bounds__(kThB) enc_lstm_bwd_kernel(EncBwdP p) {
         o.mh = ob[7 * kU + u];
       }
     }
-#else
-    const Ops o = nxt;
-#if SAT_ENC_BWD_PF2
-    nxt = nxt2;
-    nxt2 = load_ops(i + 2);
-#else
-    nxt = load_ops(i + 1);
-#endif
-#endif
     // ---- recurrent product of the previously processed step's gate gradients
     float v[kRowsB];
     {
@@ -346,14 +260,7 @@ __global__ void __launch_bounds__(kThB) enc_lstm_bwd_kernel(EncBwdP p) {
         v[r] = a.x + a.y;
       }
     }
-#if SAT_ENC_BWD8
     transpose_reduce16(v, lane);
-#else
-    transpose_reduce8(v, lane);
-#endif
-#if SAT_ENC_DRAIN_CELL && !SAT_ENC_BWD_DMA
-    vm_drain();   // (see the forward)
-#endif
     if (lead) {
       const float dh_t = v[0] + dh_c;
       const float dc_t = dc_c;
@@ -376,10 +283,8 @@ __global__ void __launch_bounds__(kThB) enc_lstm_bwd_kernel(EncBwdP p) {
       reinterpret_cast<float4*>(p.DG[d])[(int64_t)n * B * kU + bu] = dg;
       *reinterpret_cast<float4*>(&dgn[(i + 1) & 1][4 * u]) = dg;
     }
-#if SAT_ENC_BWD_DMA
     // the chunk's last step: this wave's DMA of the next chunk has landed before the barrier
     if ((i & 7) == 7) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     lds_barrier();   // LDS only: a __syncthreads would drain the DG store and the prefetch
   }
 }

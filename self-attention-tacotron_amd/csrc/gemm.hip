@@ -1229,24 +1229,6 @@ extern "C" int sat_gemm_force_plan(int32_t bm, int32_t bn, int32_t splits) {
   return SAT_OK;
 }
 
-// SAT_GEMM_LDS=0 selects the register-staged kernel for every product (A/B switch).
-static bool gemm_lds_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("SAT_GEMM_LDS");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// SAT_GEMM_SKINNY=0 sends M <= 8 products to the tile kernels (A/B switch).
-static bool gemm_skinny_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("SAT_GEMM_SKINNY");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 static void launch_splitk_reduce(const GemmP& p, hipStream_t s) {
   const int64_t total = (int64_t)p.M * p.N * p.nb;
   const int64_t work = (p.N % 4 == 0) ? total / 4 : total;
@@ -1490,15 +1472,15 @@ static int launch_lds(const SatGemmDesc* d, GemmP& p, int nb, hipStream_t s) {
 // sat_gemm splits the descriptor into two accumulating launches (gemm_split_segments).
 static bool segments_fused_ok(const SatGemmDesc* d) {
   return d->a_mode == 0 && d->b_mode == 0 && !d->colsum_out && d->k1 > 0 && d->k1 < d->K &&
-         d->k1 % BK == 0 && gemm_lds_enabled() && !t_probe &&
+         d->k1 % BK == 0 && !t_probe &&
          (!d->A2 || (d->a_sk == 1 && aligned16(d->A2) && d->a2_sm % 4 == 0)) &&
          (!d->B2 || (aligned16(d->B2) && d->b2_s % 4 == 0 && (d->b_sn == 1 || d->b_sk == 1)));
 }
 
 extern "C" int sat_gemm(const SatGemmDesc* d, void* stream);
 
-// A segmented product the fused path cannot take (k1 not a multiple of the K-tile, the LDS
-// kernel switched off by SAT_GEMM_LDS=0, operands not vector-loadable): C = [A | A2] [B ; B2]
+// A segmented product the fused path cannot take (k1 not a multiple of the K-tile, operands
+// not vector-loadable): C = [A | A2] [B ; B2]
 // as  C = alpha A[:, :k1] B[:k1] + beta C + bias + add,  then  C += alpha A[:, k1:] B[k1:]
 // (the epilogue must be linear: no activation / mul, no C2 / colsum_out).  Same result up to
 // the summation order of the two partial products.
@@ -1567,7 +1549,7 @@ extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
   if (d->C2) {
     // two output column blocks: only the LDS kernel's unsplit epilogue takes them
     SAT_CHECK_ARG(nb == 1 && !d->colsum_out && !d->mul && !d->add && d->n1 > 0 && d->n1 < d->N &&
-                      d->n1 % 128 == 0 && gemm_lds_enabled() && !t_probe,
+                      d->n1 % 128 == 0 && !t_probe,
                   "sat_gemm: C2 needs a batch-1 product without colsum_out / mul / add and "
                   "n1 %% 128 == 0");
     p.C2 = d->C2; p.c2_sm = d->c2_sm; p.n1 = d->n1;
@@ -1577,7 +1559,7 @@ extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
     if (d->A2 || d->B2) {
       // two reduction segments: A2 (dense K-contiguous A) and / or B2 (dense B, B's layout)
       SAT_CHECK_ARG(d->a_mode == 0 && d->b_mode == 0 && !d->colsum_out && d->k1 > 0 &&
-                        d->k1 < d->K && d->k1 % BK == 0 && gemm_lds_enabled() && !t_probe,
+                        d->k1 < d->K && d->k1 % BK == 0 && !t_probe,
                     "sat_gemm: A2 / B2 need a dense product, 0 < k1 < K, k1 %% 32 == 0, "
                     "no colsum_out");
       SAT_CHECK_ARG(!d->A2 || (d->a_sk == 1 && aligned16(d->A2) && d->a2_sm % 4 == 0),
@@ -1624,7 +1606,7 @@ extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
     SAT_CHECK_ARG(nb <= 1 || d->bias_sbatch != 0 || d->b_sbatch == 0,
                   "sat_gemm: colsum_out of a batched product with a batch-strided B needs "
                   "bias_sbatch (one [N] row per batch)");
-    if (gemm_lds_enabled()) {
+    {
       p.cs_out = d->colsum_out;
       p.cs_sbatch = d->bias_sbatch;     // batch b's sums at colsum_out + b * bias_sbatch
       p.bias_sbatch = 0;
@@ -1658,8 +1640,7 @@ extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
     return colsum_alpha(d->B, d->b_sk, d->K, d->N, d->colsum_out, d->alpha, d->beta, d->ws, s);
   }
   if (nb == 1 && d->a_mode == 0 && d->b_mode == 0 && !t_probe && d->M <= kSkinnyM && d->N > 1 &&
-      d->K > 1 && !d->mul && (int64_t)d->M * d->K * 4 + 4 * kSkinnyM * 16 * 4 <= 64 * 1024 &&
-      gemm_skinny_enabled()) {
+      d->K > 1 && !d->mul && (int64_t)d->M * d->K * 4 + 4 * kSkinnyM * 16 * 4 <= 64 * 1024) {
     const size_t shm = ((size_t)d->M * d->K + 4 * kSkinnyM * 16) * sizeof(float);
     hipLaunchKernelGGL(gemm_skinny_kernel, dim3(ceil_div(d->N, 16)), dim3(256), shm, s, p);
     SAT_LAUNCH_CHECK("sat_gemm (skinny)");
@@ -1678,7 +1659,7 @@ extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
     SAT_LAUNCH_CHECK("sat_gemm (degenerate shape)");
     return SAT_OK;
   }
-  if (gemm_lds_enabled()) {
+  {
     const int r = launch_lds(d, p, nb, s);
     if (r != 1) return r;   // 1: operand layout not vector-loadable, use the register path
   }

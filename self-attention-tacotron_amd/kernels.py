@@ -58,8 +58,8 @@ _AUX = {}
 def aux_stream(device, which: int = 0) -> torch.cuda.Stream:
     """The step's second stream (independent branches beside the encoder, forward and backward),
     one per device, made on first use -- the eager warm-up before any graph capture; the GEMM
-    split-K and column-reduction scratch are keyed per stream already.  ``which=1``: a third
-    stream (the encoder backward's weight-gradient branches, SAT_AUX2=1)."""
+    split-K and column-reduction scratch are keyed per stream already.  ``which`` > 0: further
+    streams (2: the conv bank's weight-gradient side branch of the encoder backward)."""
     key = (device.index, which)
     s = _AUX.get(key)
     if s is None:

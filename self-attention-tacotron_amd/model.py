@@ -12,7 +12,6 @@ except the attention energies which the backward recomputes to avoid a [T', B, N
 from __future__ import annotations
 
 import math
-import os
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -158,11 +157,8 @@ def encoder_fwd(P, bn: BNState, hp, d: PR.Dims, ids, lengths, masks, training, w
     bet = _contig_span(P, [f"{n}/bn/beta" for n in names])
     mp = torch.empty_like(bank)
     # BN + ReLU and the max-pool (module.py:79-80) in one pass over the bank
-    fused = os.environ.get("SAT_BANK_POOL_FUSED", "1") == "1"       # 0: two launches (A/B)
     st_bank = _bn(bank_pre.view(-1, KC), bank.view(-1, KC), gam, bet, bn, f"{names[0]}/bn", KC, True,
-                  training, ws, pool=(bank_pre, bank, mp) if fused else None)
-    if not fused:
-        K.maxpool2(bank, mp)                                          # module.py:80
+                  training, ws, pool=(bank_pre, bank, mp))
     p1_pre = K.conv1d(mp, P["encoder/cbhg/proj1/kernel"], P["encoder/cbhg/proj1/bias"])
     p1 = torch.empty_like(p1_pre)
     st_p1 = _bn(p1_pre.view(-1, d.proj1), p1.view(-1, d.proj1), P["encoder/cbhg/proj1/bn/gamma"],

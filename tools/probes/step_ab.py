@@ -2,7 +2,7 @@
 baselines / extras) once per variant per round, interleaved, and prints ms/step and the loss.
 
 Usage: python tools/probes/step_ab.py ROUNDS NAME=ENV[,ENV...] [NAME=...]
-  e.g. python tools/probes/step_ab.py 2 base= late=SAT_DEC_WGRAD_FORK=pg
+  e.g. python tools/probes/step_ab.py 2 base= model=SAT_GEMM_PLAN_TABLE=0
 """
 import json
 import os
