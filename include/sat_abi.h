@@ -43,8 +43,9 @@ extern "C" {
  * and cumulative weights of ForwardAttention (trailing fields of SatAttnStep / SatAttnStepBwd,
  * sat_attn_agent_bwd); 10: SatAttnStep.agent_b_sb, the speaker-vector kernels (sat_rows_bias_fwd /
  * _bwd, sat_ctx_tail_fill); 11: the summary image kernels (sat_image_minmax / sat_image_render);
- * 12: the audio front end (SatMelSpec, sat_melspec, sat_mel_stats). */
-#define SAT_ABI_VERSION 12
+ * 12: the audio front end (SatMelSpec, sat_melspec, sat_mel_stats); 13: the silence trim
+ * (sat_trim_bounds) and SatMelSpec.offsets / offsets_host (a segment of each row). */
+#define SAT_ABI_VERSION 13
 
 /* ---------------------------------------------------------------- library */
 int sat_version(void);                         /* 100*major + minor */
@@ -1016,6 +1017,12 @@ int sat_image_render(const float* src, int64_t src_n, const int64_t* base, const
  *     outside 64..4096; SAT_ERR_ARGUMENT: win > n_fft, hop < 1, num_freq != n_fft/2 + 1, a null
  *     pointer (mag_out excepted), any lengths[b] <= n_fft/2 (the reflection would run past the
  *     utterance) or > wav_stride, F_max below the largest frame count, B > 65535.
+ *     offsets (device int32, nullable) with its host copy offsets_host: utterance b is then the
+ *     segment wav[b] + offsets[b] of lengths[b] samples, and the reflection stays inside that
+ *     segment -- melspectrogram(trim(wav)) of preprocess/vctk.py:129-134 without a copy of the
+ *     trimmed waveform.  With offsets == NULL the results are bit-identical to ABI 12's.  Also
+ *     refused (SAT_ERR_ARGUMENT): only one of offsets / offsets_host, offsets_host[b] < 0,
+ *     offsets_host[b] + lengths_host[b] > wav_stride.
  *   sat_mel_stats: out[b][0..3][m] (fp64 [B][4][M]) = min, max, sum and sum of squares of
  *     mel[b][f][m] over f < min(frames[b], F_max) (device int32); +inf, -inf, 0, 0 when there is no
  *     frame.  Sums in fp64 in a fixed order; corpus totals are the caller's. */
@@ -1035,10 +1042,39 @@ typedef struct SatMelSpec {
   const int32_t* band_hi;
   float* out;                     /* [B][F_max][num_mels] */
   float* mag_out;                 /* [B][F_max][num_freq] or NULL */
+  const int32_t* offsets;         /* device, first sample of each segment, or NULL */
+  const int32_t* offsets_host;    /* host copy of offsets (NULL with it) */
 } SatMelSpec;
 int sat_melspec(const SatMelSpec* d, void* stream);
 int sat_mel_stats(const float* mel, const int32_t* frames, int32_t B, int32_t F_max, int32_t M,
                   double* out, void* stream);
+
+/* ---------------------------------------------------------------- silence trim
+ * Audio.trim (utils/audio.py:40-49): librosa 0.6 effects.trim, then num_silent_frames of margin.
+ * For utterance b with L = lengths[b] samples y, p = frame_length / 2 (integer division):
+ *   ypad = y reflect-padded by p on both sides, taken by index on the unpadded row (i -> -i below
+ *   0, i -> 2 (L - 1) - i from L on); F = 1 + (L + 2 p - frame_length) / hop frames;
+ *   ms[f] = mean over j < frame_length of ypad[f*hop + j]^2 (fp32, a fixed summation order);
+ *   frame f is non-silent iff max(1e-10, ms[f]) > max(1e-10, max_f ms[f]) * 10^(-top_db / 10),
+ *   which is librosa's 10 log10(max(1e-10, ms[f])) - 10 log10(max(1e-10, max ms)) > -top_db (so an
+ *   all-zero utterance is non-silent throughout, as there);
+ *   index = (first*hop, min(L, (last + 1)*hop)) over the non-silent frames, (0, 0) without one;
+ *   bounds[b] = (max(index0 - pad_samples, 0), min(index1 + pad_samples, L)).
+ * pad_samples is the reference's num_sil_samples, computed by the caller.  frame_ms [B][ms_stride]
+ * (device) receives ms (columns F..ms_stride-1 are left as they are); it is the entry's scratch
+ * and a test's window.  Where frame_length is a multiple of hop the frame sums are formed from
+ * per-hop partial sums, so a sample is read about once; every other (frame_length >= 2, hop >= 1)
+ * is summed frame by frame.  One call covers the batch: a frame-energy launch over
+ * (ceil(F_max / 64), B) and a per-utterance max / first / last launch.  lengths (device) is what
+ * the kernels read, lengths_host what the entry checks; a device length the entry would have
+ * refused gives bounds (0, 0).  Deterministic: no atomics, no order-dependent float reduction.
+ * Refused before anything is launched (SAT_ERR_ARGUMENT): B outside 0..65535, hop < 1,
+ * frame_length < 2, top_db negative or not finite, pad_samples < 0, a null pointer (B > 0), any
+ * lengths_host[b] <= frame_length / 2 or > wav_stride, ms_stride below the largest F. */
+int sat_trim_bounds(const float* wav, const int32_t* lengths, const int32_t* lengths_host,
+                    int32_t B, int32_t wav_stride, int32_t frame_length, int32_t hop, float top_db,
+                    int32_t pad_samples, int32_t* bounds, float* frame_ms, int32_t ms_stride,
+                    void* stream);
 
 /* ---------------------------------------------------------------- dataset records (host)
  * TFRecord framing of the dataset path: datasets/ljspeech/dataset.py:96-112 reads

@@ -194,7 +194,7 @@ SatAttnStep = _struct("SatAttnStep", """
 SatMelSpec = _struct("SatMelSpec", """
     i32:B i32:wav_stride i32:n_fft i32:hop i32:win i32:num_mels i32:num_freq i32:F_max
     f32:ref_level_db f32:amp_floor ptr:wav ptr:lengths ptr:lengths_host ptr:window ptr:twiddle
-    ptr:basis ptr:band_lo ptr:band_hi ptr:out ptr:mag_out""")
+    ptr:basis ptr:band_lo ptr:band_hi ptr:out ptr:mag_out ptr:offsets ptr:offsets_host""")
 
 # name -> argtypes (restype is int for all but sat_last_error_string)
 SIGNATURES = {
@@ -282,6 +282,7 @@ SIGNATURES.update({
     "sat_image_render": [_P, _I64, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     "sat_melspec": [ctypes.POINTER(SatMelSpec), _P],
     "sat_mel_stats": [_P, _P, _I32, _I32, _I32, _P, _P],
+    "sat_trim_bounds": [_P, _P, _P, _I32, _I32, _I32, _I32, _F, _I32, _P, _P, _I32, _P],
 })
 
 RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
@@ -303,7 +304,7 @@ RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
 
 _lib: Optional[ctypes.CDLL] = None
 # include/sat_abi.h SAT_ABI_VERSION this binding's structs follow
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 def load(path: str = LIB_PATH) -> ctypes.CDLL:

@@ -1,14 +1,21 @@
 """Audio front end: ``utils/audio.py`` without librosa / scipy.
 
 ``Audio(hparams)`` keeps the reference's surface (``utils/audio.py:23-73``): ``_stft_parameters``,
-``_build_mel_basis``, ``load_wav``, ``save_wav``, ``melspectrogram``, ``normalize_mel``,
+``_build_mel_basis``, ``load_wav``, ``save_wav``, ``trim``, ``melspectrogram``, ``normalize_mel``,
 ``_amp_to_db``, ``_linear_to_mel``.  The feature extraction itself -- reflect padding, framing,
 window, FFT, magnitude, mel projection, dB -- is one libsat_hip launch (``csrc/audio.hip``) for a
 whole batch of utterances (``melspectrogram_batch``); torch only allocates and copies.  There is
-no host fallback: without the library or a GPU ``melspectrogram`` raises.
+no host fallback: without the library or a GPU ``melspectrogram`` and ``trim`` raise.
 
-Not carried over: ``trim`` (librosa.effects.trim, used only by the VCTK preprocessing) and
-resampling in ``load_wav`` (a file at another rate raises ``ValueError``).
+``trim`` is librosa 0.6's ``effects.trim`` plus ``num_silent_frames`` of margin
+(``utils/audio.py:40-49``), decided on the GPU for a whole batch (``trim_batch``,
+``csrc/trim.hip``): frame mean squares of the reflect-padded utterance, the dB test against the
+loudest frame, first and last non-silent frame.  ``trim_batch`` returns the uploaded waveforms and
+their ``(start, stop)`` bounds; ``melspectrogram_batch(wav, bounds=...)`` then reads each
+utterance's segment in place, so the VCTK path is one upload, the trim launch, one read-back of
+the bounds (the host needs the lengths and the largest frame count) and one mel launch.
+
+Not carried over: resampling in ``load_wav`` (a file at another rate raises ``ValueError``).
 """
 
 from __future__ import annotations
@@ -138,6 +145,13 @@ class Audio:
             return K.transpose(mel[0])
         return np.ascontiguousarray(mel[0].cpu().numpy().T)
 
+    def trim(self, wav):
+        """``wav[start:stop]`` of ``trim_batch``'s bounds: numpy in, numpy out -- device tensor
+        in, a view of it out."""
+        _, bounds = self.trim_batch([wav])
+        start, stop = (int(v) for v in bounds.cpu().numpy()[0])
+        return wav[start:stop]
+
     def normalize_mel(self, S):
         return (S - self.average_mel_level_db) / self.stddev_mel_level_db
 
@@ -174,25 +188,19 @@ class Audio:
             self._plans[key] = plan
         return plan
 
-    def melspectrogram_batch(self, wavs, return_magnitudes: bool = False):
-        """A list of 1-D waveforms (numpy arrays or tensors) through one padded upload and one
-        launch: ``(mel [B, F_max, num_mels], frames [B] int32)`` on the device, rows past an
-        utterance's frame count zero; with ``return_magnitudes`` also ``[B, F_max, num_freq]``."""
+    def _upload(self, wavs, what):
+        """``(wav [B, stride] on the device, lengths)`` of a list of 1-D waveforms (numpy arrays
+        or tensors): one padded upload."""
         import torch
         from . import kernels as K
         if len(wavs) == 0:
-            raise ValueError("melspectrogram_batch: no waveform")
-        n_fft, hop, win = self._stft_parameters()
-        if hop < 1:
-            raise ValueError(f"frame_shift_ms gives a hop of {hop} samples")
+            raise ValueError(f"{what}: no waveform")
         on_dev = [isinstance(w, torch.Tensor) for w in wavs]
         device = wavs[0].device if on_dev[0] and wavs[0].is_cuda else self._dev()
         lengths = [int(w.shape[0]) for w in wavs]
         if any(w.ndim != 1 for w in wavs):
-            raise ValueError("melspectrogram_batch: waveforms must be 1-D")
+            raise ValueError(f"{what}: waveforms must be 1-D")
         B, stride = len(wavs), max(lengths)
-        frames = [1 + L // hop for L in lengths]
-        F_max = max(frames)
         if all(on_dev):
             wav = K.zeros(B, stride, device=device)
             for b, w in enumerate(wavs):
@@ -202,7 +210,63 @@ class Audio:
             for b, w in enumerate(wavs):
                 host[b, :lengths[b]] = w.cpu().numpy() if on_dev[b] else w
             wav = torch.from_numpy(host).to(device)
-        meta = torch.from_numpy(np.array([lengths, frames], np.int32)).to(device)
+        return wav, lengths
+
+    def trim_batch(self, wavs):
+        """A list of 1-D waveforms through one padded upload and the trim launch:
+        ``(wav [B, stride], bounds [B, 2] int32)`` on the device, ``bounds[b] = (start, stop)`` of
+        utterance b under ``hparams.trim_top_db`` / ``trim_frame_length`` / ``trim_hop_length``
+        and ``num_silent_frames`` (``utils/audio.py:40-49``).  Nothing is read back."""
+        import torch
+        from . import kernels as K
+        hp = self.hparams
+        frame_length, hop = int(hp.trim_frame_length), int(hp.trim_hop_length)
+        if frame_length < 2 or hop < 1:
+            raise ValueError(f"trim_frame_length {frame_length} / trim_hop_length {hop}: need a "
+                             "frame of at least 2 samples and a hop of at least 1")
+        pad_samples = int(hp.num_silent_frames * hp.frame_shift_ms * hp.sample_rate / 1000)
+        wav, lengths = self._upload(wavs, "trim_batch")
+        B = len(lengths)
+        F_max = 1 + (max(lengths) + 2 * (frame_length // 2) - frame_length) // hop
+        dlen = torch.from_numpy(np.array(lengths, np.int32)).to(wav.device)
+        bounds = torch.empty(B, 2, dtype=torch.int32, device=wav.device)
+        frame_ms = torch.empty(B, max(F_max, 1), device=wav.device)
+        K.trim_bounds(wav, dlen, lengths, frame_length=frame_length, hop=hop,
+                      top_db=hp.trim_top_db, pad_samples=pad_samples, bounds=bounds,
+                      frame_ms=frame_ms)
+        return wav, bounds
+
+    def melspectrogram_batch(self, wavs, bounds=None, return_magnitudes: bool = False):
+        """A list of 1-D waveforms (numpy arrays or tensors) through one padded upload and one
+        launch: ``(mel [B, F_max, num_mels], frames [B] int32)`` on the device, rows past an
+        utterance's frame count zero; with ``return_magnitudes`` also ``[B, F_max, num_freq]``.
+
+        With ``bounds`` ([B, 2] int32, ``trim_batch``'s device tensor or a host array) utterance b
+        is ``wavs[b][start:stop]``, read in place; ``wavs`` may then also be ``trim_batch``'s
+        ``[B, stride]`` device tensor, which is used as it is."""
+        import torch
+        from . import kernels as K
+        n_fft, hop, win = self._stft_parameters()
+        if hop < 1:
+            raise ValueError(f"frame_shift_ms gives a hop of {hop} samples")
+        if bounds is not None and isinstance(wavs, torch.Tensor) and wavs.ndim == 2:
+            wav, row_lengths = wavs, [int(wavs.shape[1])] * int(wavs.shape[0])
+        else:
+            wav, row_lengths = self._upload(wavs, "melspectrogram_batch")
+        device, B = wav.device, len(row_lengths)
+        offsets = None
+        if bounds is None:
+            lengths = row_lengths
+        else:
+            bh = bounds.cpu().numpy() if isinstance(bounds, torch.Tensor) else np.asarray(bounds)
+            if bh.shape != (B, 2):
+                raise ValueError(f"melspectrogram_batch: bounds {bh.shape}, expected ({B}, 2)")
+            offsets = [int(v) for v in bh[:, 0]]
+            lengths = [int(e) - int(s) for s, e in bh]
+        frames = [1 + L // hop for L in lengths]
+        F_max = max(frames)
+        rows = [lengths, frames] if offsets is None else [lengths, frames, offsets]
+        meta = torch.from_numpy(np.array(rows, np.int32)).to(device)
         plan = self._plan(device)
         out = torch.empty(B, F_max, self.hparams.num_mels, device=device)
         mag = torch.empty(B, F_max, self.hparams.num_freq, device=device) \
@@ -210,7 +274,8 @@ class Audio:
         K.melspec(wav, meta[0], lengths, n_fft=n_fft, hop=hop, win=win, window=plan["window"],
                   twiddle=plan["twiddle"], basis=plan["basis"], band_lo=plan["band_lo"],
                   band_hi=plan["band_hi"], ref_level_db=self.hparams.ref_level_db,
-                  amp_floor=AMP_FLOOR, out=out, mag_out=mag)
+                  amp_floor=AMP_FLOOR, out=out, mag_out=mag,
+                  **({} if offsets is None else dict(offsets=meta[2], offsets_host=offsets)))
         return (out, meta[1], mag) if return_magnitudes else (out, meta[1])
 
     def mel_statistics(self, mel, frames):

@@ -11,7 +11,9 @@
 // magnitudes) = 12 n_fft + 8 bytes: 24 KB at 2048 (6 workgroups per CU), 48 KB at 4096 (3).
 // The separation, the magnitude, the band sum and the logarithm are done in fp64 (a few hundred
 // operations per frame beside the 11 k butterflies), so the FFT's own fp32 rounding is the only
-// error of the result -- DESIGN.md "Audio front end".
+// error of the result -- DESIGN.md "Audio front end".  With SatMelSpec.offsets an utterance is a
+// segment of its row (the silence trim's bounds, csrc/trim.hip): the row pointer moves by the
+// offset and everything else, the reflection at the segment's ends included, is as before.
 #include "sat_common.h"
 
 using namespace sat;
@@ -19,7 +21,7 @@ using namespace sat;
 namespace {
 
 struct MelSpecP {
-  const float* wav; const int32_t* lengths;
+  const float* wav; const int32_t* lengths; const int32_t* offsets;
   const float* window; const float2* twiddle;
   const float* basis; const int32_t* band_lo; const int32_t* band_hi;
   float* out; float* mag_out;
@@ -45,9 +47,10 @@ __global__ void __launch_bounds__(256) melspec_kernel(MelSpecP p) {
   float* mag = reinterpret_cast<float*>(tw);            // later: 2 x nf magnitudes
   const int b = blockIdx.y, f0 = 2 * blockIdx.x, f1 = f0 + 1;
 
-  // a length the entry would have refused (device copy out of step with the host's) reads nothing
-  int L = p.lengths[b];
-  int frames = (L > half_n && L <= p.wav_stride) ? 1 + L / p.hop : 0;
+  // a length or an offset the entry would have refused (device copy out of step with the host's)
+  // reads nothing
+  const int L = p.lengths[b], off = p.offsets ? p.offsets[b] : 0;
+  int frames = (L > half_n && off >= 0 && (int64_t)off + L <= p.wav_stride) ? 1 + L / p.hop : 0;
   if (frames > p.F_max) frames = p.F_max;
   float* out0 = p.out + ((int64_t)b * p.F_max + f0) * p.num_mels;
   float* mag0 = p.mag_out ? p.mag_out + ((int64_t)b * p.F_max + f0) * nf : nullptr;
@@ -62,7 +65,7 @@ __global__ void __launch_bounds__(256) melspec_kernel(MelSpecP p) {
   }
   const bool have1 = f1 < frames;
 
-  const float* y = p.wav + (int64_t)b * p.wav_stride;
+  const float* y = p.wav + (int64_t)b * p.wav_stride + off;
   const int shift = 32 - p.log2n;
   for (int j = tid; j < n; j += 256) {
     const float w = p.window[j];
@@ -184,6 +187,8 @@ extern "C" int sat_melspec(const SatMelSpec* d, void* stream) {
   if (d->B == 0) return SAT_OK;
   SAT_CHECK_ARG(d->wav && d->lengths && d->lengths_host && d->window && d->twiddle && d->basis &&
                 d->band_lo && d->band_hi && d->out, "sat_melspec: null pointer");
+  SAT_CHECK_ARG(!d->offsets == !d->offsets_host,
+                "sat_melspec: offsets and offsets_host go together (both or neither)");
   SAT_CHECK_ARG((reinterpret_cast<uintptr_t>(d->twiddle) & 7) == 0,
                 "sat_melspec: twiddle table must be 8-byte aligned");
   int max_frames = 0;
@@ -193,13 +198,18 @@ extern "C" int sat_melspec(const SatMelSpec* d, void* stream) {
                   "run past the utterance)", b, L, n / 2);
     SAT_CHECK_ARG(L <= d->wav_stride, "sat_melspec: lengths[%d] = %d > wav_stride %d", b, L,
                   d->wav_stride);
+    if (d->offsets) {
+      const int off = d->offsets_host[b];
+      SAT_CHECK_ARG(off >= 0 && (int64_t)off + L <= d->wav_stride, "sat_melspec: segment %d = "
+                    "[%d, %d + %d) leaves the row of %d samples", b, off, off, L, d->wav_stride);
+    }
     max_frames = std::max(max_frames, 1 + L / d->hop);
   }
   SAT_CHECK_ARG(d->F_max >= max_frames, "sat_melspec: F_max %d < the largest frame count %d",
                 d->F_max, max_frames);
   int log2n = 0;
   while ((1 << log2n) < n) ++log2n;
-  MelSpecP p{d->wav, d->lengths, d->window, reinterpret_cast<const float2*>(d->twiddle), d->basis,
+  MelSpecP p{d->wav, d->lengths, d->offsets, d->window, reinterpret_cast<const float2*>(d->twiddle), d->basis,
              d->band_lo, d->band_hi, d->out, d->mag_out, d->B, d->wav_stride, n, log2n, d->hop,
              d->num_mels, d->num_freq, d->F_max, d->ref_level_db, d->amp_floor};
   const size_t lds = (size_t)12 * n + 8;

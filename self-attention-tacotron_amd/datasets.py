@@ -22,6 +22,14 @@ bucket 0 (kept as the reference has it).  A window is emitted as padded batches 
 ``window_size`` elements; the rest are flushed at the end of the input in order of each key's
 first appearance.  Padding: source 0, mel ``silence_mel_level_db``, done 1, masks 0, scalars 0.
 
+VCTK (``datasets/vctk/dataset.py``): ``VCTKDatasetSource`` reads the source record with
+``speaker_id, age, gender`` (:64-96) into ``VCTKSourceData`` (:31-39; ``hparams.source ==
+'phone'`` selects the record's phone fields, :143-148) and shares everything else -- the target
+preparation, ``ZippedDataset``, ``BatchedDataset`` -- with LJSpeech; ``merge_target_to_source``
+gives ``VCTKSourceDataForPrediction`` (:49-61).  The reference's padding values for the three
+speaker fields (0, 0, -1, :299-301) pad scalars, which a padded batch never does: a short last
+batch simply has fewer rows.
+
 Randomness (``shuffle``) uses ``numpy.random.default_rng(seed)`` -- the same buffer algorithm as
 tf.data's shuffle (fill ``buffer_size``, emit a uniformly chosen slot, refill it), not its
 random stream.
@@ -51,6 +59,19 @@ class MelData(namedtuple("MelData", ["id", "key", "mel", "mel_width", "target_le
 class SourceDataForPrediction(namedtuple("SourceDataForPrediction",
                                          ["id", "key", "source", "source_length", "text", "mel",
                                           "mel_width", "target_length"])):
+    pass
+
+
+class VCTKSourceData(namedtuple("VCTKSourceData",
+                                ["id", "key", "source", "source_length", "speaker_id", "age",
+                                 "gender", "text"])):
+    pass
+
+
+class VCTKSourceDataForPrediction(namedtuple("VCTKSourceDataForPrediction",
+                                             ["id", "key", "source", "source_length",
+                                              "speaker_id", "age", "gender", "text", "mel",
+                                              "mel_width", "target_length"])):
     pass
 
 
@@ -185,6 +206,21 @@ def prepare_source(s: R.PreprocessedSourceData) -> SourceData:
     return SourceData(s.id, s.key, s.source, s.source_length, s.text)
 
 
+def prepare_vctk_source(s: R.PreprocessedVCTKSourceData, hparams) -> VCTKSourceData:
+    """datasets/vctk/dataset.py:143-148: the phone fields under ``hparams.source == 'phone'``,
+    the character fields under any other value."""
+    if hparams.source == 'phone':
+        for name in ("phone", "phone_length", "phone_txt"):
+            if getattr(s, name) is None:
+                raise ValueError(f"hparams.source is 'phone' but record {s.key!r} has no "
+                                 f"{name!r} field (records written without a phone front end "
+                                 "need source='char')")
+        return VCTKSourceData(s.id, s.key, s.phone, s.phone_length, s.speaker_id, s.age,
+                              s.gender, s.phone_txt)
+    return VCTKSourceData(s.id, s.key, s.source, s.source_length, s.speaker_id, s.age, s.gender,
+                          s.text)
+
+
 def _pad_stack(arrays, pad_value, dtype):
     n = max(a.shape[0] for a in arrays)
     out = np.full((len(arrays), n) + arrays[0].shape[1:], pad_value, dtype)
@@ -198,11 +234,17 @@ def padded_batch(elems, hparams):
     src = [e[0] for e in elems]
     tgt = [e[1] for e in elems]
     sil = hparams.silence_mel_level_db
-    s = SourceData(id=np.array([x.id for x in src], np.int64),
-                   key=np.array([x.key for x in src], object),
-                   source=_pad_stack([x.source for x in src], 0, np.int64),
-                   source_length=np.array([x.source_length for x in src], np.int64),
-                   text=np.array([x.text for x in src], object))
+    cols = dict(id=np.array([x.id for x in src], np.int64),
+                key=np.array([x.key for x in src], object),
+                source=_pad_stack([x.source for x in src], 0, np.int64),
+                source_length=np.array([x.source_length for x in src], np.int64),
+                text=np.array([x.text for x in src], object))
+    if isinstance(src[0], VCTKSourceData):
+        s = VCTKSourceData(speaker_id=np.array([x.speaker_id for x in src], np.int64),
+                           age=np.array([x.age for x in src], np.int64),
+                           gender=np.array([x.gender for x in src], np.int64), **cols)
+    else:
+        s = SourceData(**cols)
     t = MelData(id=np.array([x.id for x in tgt], np.int64),
                 key=np.array([x.key for x in tgt], object),
                 mel=_pad_stack([x.mel for x in tgt], sil, np.float32),
@@ -253,6 +295,26 @@ class DatasetSource:
         def gen():
             for s, t in zip(src, tgt):
                 yield (prepare_source(R.parse_preprocessed_source_data(s)),
+                       prepare_target(R.parse_preprocessed_mel_data(t), hp))
+        return ZippedDataset(_Dataset(gen), hp)
+
+
+class VCTKDatasetSource(DatasetSource):
+    """datasets/vctk/dataset.py:99-201: the VCTK source record, the shared target."""
+
+    @staticmethod
+    def create_from_tfrecord_files(source_files, target_files, hparams, cycle_length=4,
+                                   buffer_output_elements=None, prefetch_input_elements=None):
+        return VCTKDatasetSource(interleave_files(list(source_files), cycle_length),
+                                 interleave_files(list(target_files), cycle_length), hparams)
+
+    def prepare_and_zip(self) -> "ZippedDataset":
+        hp = self.hparams
+        src, tgt = self.source, self.target
+
+        def gen():
+            for s, t in zip(src, tgt):
+                yield (prepare_vctk_source(R.parse_preprocessed_vctk_source_data(s), hp),
                        prepare_target(R.parse_preprocessed_mel_data(t), hp))
         return ZippedDataset(_Dataset(gen), hp)
 
@@ -354,27 +416,37 @@ class BatchedDataset(DatasetBase):
 
     def merge_target_to_source(self):
         """:306-320."""
-        def convert(s: SourceData, t: MelData):
+        def convert(s, t: MelData):
+            if isinstance(s, VCTKSourceData):
+                return VCTKSourceDataForPrediction(*s, t.mel, t.mel_width, t.target_length), t
             return SourceDataForPrediction(s.id, s.key, s.source, s.source_length, s.text,
                                            t.mel, t.mel_width, t.target_length), t
         return self.apply(self.dataset.map(convert), self.hparams)
 
 
+_LJSPEECH_NAMES = ("ljspeech.dataset.DatasetSource", "datasets.ljspeech.dataset.DatasetSource")
+_VCTK_NAMES = ("vctk.dataset.DatasetSource", "datasets.vctk.dataset.DatasetSource")
+
+
 def dataset_factory(source, target, hparams):
     """datasets/dataset_factory.py:15-23 with the LJSpeech entry enabled (it is commented out
-    in the fork, :12); other names raise ValueError as the reference's factory would."""
-    if hparams.dataset in ("ljspeech.dataset.DatasetSource", "datasets.ljspeech.dataset.DatasetSource"):
+    in the fork, :12) and the VCTK one; other names raise ValueError as the reference's factory
+    would."""
+    if hparams.dataset in _LJSPEECH_NAMES:
         return DatasetSource(source, target, hparams)
+    if hparams.dataset in _VCTK_NAMES:
+        return VCTKDatasetSource(source, target, hparams)
     raise ValueError(f"Unknown dataset: {hparams.dataset}")
 
 
 def create_from_tfrecord_files(source_files, target_files, hparams, cycle_length=4,
                                buffer_output_elements=None, prefetch_input_elements=None):
     """datasets/dataset_factory.py:26-32 (LJSpeech entry enabled)."""
-    if hparams.dataset in ("ljspeech.dataset.DatasetSource", "datasets.ljspeech.dataset.DatasetSource"):
-        return DatasetSource.create_from_tfrecord_files(source_files, target_files, hparams,
-                                                        cycle_length, buffer_output_elements,
-                                                        prefetch_input_elements)
+    for names, cls in ((_LJSPEECH_NAMES, DatasetSource), (_VCTK_NAMES, VCTKDatasetSource)):
+        if hparams.dataset in names:
+            return cls.create_from_tfrecord_files(source_files, target_files, hparams,
+                                                  cycle_length, buffer_output_elements,
+                                                  prefetch_input_elements)
     raise ValueError(f"Unknown dataset: {hparams.dataset}")
 
 
@@ -389,3 +461,10 @@ def train_input_fn(hparams, source_files, target_files, seed: Optional[int] = No
                     .shuffle(hparams.suffle_buffer_size, seed).group_by_batch()
                     .prefetch(hparams.prefetch_buffer_size))
     return input_fn
+
+
+class vctk:
+    """The reference's names for the VCTK classes (``datasets.vctk.dataset``)."""
+    DatasetSource = VCTKDatasetSource
+    SourceData = VCTKSourceData
+    SourceDataForPrediction = VCTKSourceDataForPrediction

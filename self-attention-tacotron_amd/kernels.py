@@ -1100,16 +1100,19 @@ def image_render(src, base, rows, cols, col_stride, minmax, canvas, rows_host=No
 
 # ---- audio front end (csrc/audio.hip; sat_amd/audio.py)
 def melspec(wav, lengths, lengths_host, *, n_fft, hop, win, window, twiddle, basis, band_lo,
-            band_hi, ref_level_db, amp_floor, out, mag_out=None):
+            band_hi, ref_level_db, amp_floor, out, mag_out=None, offsets=None, offsets_host=None):
     """Batch of waveforms ``wav`` [B, stride] -> mel dB ``out`` [B, F_max, num_mels] (and the
-    magnitudes ``mag_out`` [B, F_max, num_freq]) in one launch; see include/sat_abi.h.  Only
-    dtypes and buffer sizes are checked here: what the entry refuses, it refuses itself."""
+    magnitudes ``mag_out`` [B, F_max, num_freq]) in one launch; see include/sat_abi.h.  With
+    ``offsets`` (device int32 [B]) and its host copy, utterance b is the segment of ``lengths[b]``
+    samples that starts at ``wav[b, offsets[b]]``.  Only dtypes and buffer sizes are checked here:
+    what the entry refuses, it refuses itself."""
     for name, t in (("wav", wav), ("window", window), ("twiddle", twiddle), ("basis", basis),
                     ("out", out), ("mag_out", mag_out)):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
             raise ValueError(f"melspec: {name} must be a contiguous float32 tensor")
-    for name, t in (("lengths", lengths), ("band_lo", band_lo), ("band_hi", band_hi)):
-        if t.dtype != torch.int32 or not t.is_contiguous():
+    for name, t in (("lengths", lengths), ("band_lo", band_lo), ("band_hi", band_hi),
+                    ("offsets", offsets)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
             raise ValueError(f"melspec: {name} must be a contiguous int32 tensor")
     if wav.dim() != 2 or basis.dim() != 2 or out.dim() != 3:
         raise ValueError("melspec: wav [B, stride], basis [num_mels, num_freq], out [B, F, num_mels]")
@@ -1124,13 +1127,18 @@ def melspec(wav, lengths, lengths_host, *, n_fft, hop, win, window, twiddle, bas
         raise ValueError("melspec: lengths need B entries, band_lo / band_hi num_mels entries")
     if window.numel() < n_fft or twiddle.numel() < n_fft:
         raise ValueError("melspec: window and twiddle table need n_fft floats each")
+    if (offsets is not None and offsets.numel() != B) or (offsets_host is not None
+                                                          and len(offsets_host) != B):
+        raise ValueError("melspec: offsets need B entries")
     keep, host = _host_i32(lengths_host, B)
+    keep_off, off_host = _host_i32(offsets_host, B)
     d = _lib.SatMelSpec(B=B, wav_stride=stride, n_fft=int(n_fft), hop=int(hop), win=int(win),
                         num_mels=num_mels, num_freq=num_freq, F_max=F_max,
                         ref_level_db=float(ref_level_db), amp_floor=float(amp_floor),
                         wav=_p(wav), lengths=_p(lengths), lengths_host=host, window=_p(window),
                         twiddle=_p(twiddle), basis=_p(basis), band_lo=_p(band_lo),
-                        band_hi=_p(band_hi), out=_p(out), mag_out=_p(mag_out) or None)
+                        band_hi=_p(band_hi), out=_p(out), mag_out=_p(mag_out) or None,
+                        offsets=_p(offsets) or None, offsets_host=off_host)
     _lib.check(_lib.load().sat_melspec(ctypes.byref(d), _stream()), "sat_melspec")
 
 
@@ -1145,3 +1153,25 @@ def mel_stats(mel, frames, out):
     if out.dtype != torch.float64 or not out.is_contiguous() or out.shape != (B, 4, M):
         raise ValueError("mel_stats: out must be a contiguous float64 [B, 4, M] tensor")
     _lib.call("sat_mel_stats", _p(mel), _p(frames), B, F_max, M, _p(out), _stream())
+
+
+def trim_bounds(wav, lengths, lengths_host, *, frame_length, hop, top_db, pad_samples, bounds,
+                frame_ms):
+    """Silence-trim bounds of a batch of waveforms ``wav`` [B, stride] in one entry call:
+    ``bounds`` [B, 2] int32 = (start, stop) of each utterance, ``frame_ms`` [B, ms_stride] float32
+    the frame mean squares it is decided from; see include/sat_abi.h.  Only dtypes and buffer
+    sizes are checked here: what the entry refuses, it refuses itself."""
+    for name, t in (("wav", wav), ("frame_ms", frame_ms)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
+            raise ValueError(f"trim_bounds: {name} must be a contiguous float32 [B, n] tensor")
+    for name, t in (("lengths", lengths), ("bounds", bounds)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f"trim_bounds: {name} must be a contiguous int32 tensor")
+    B, stride = wav.shape
+    if (lengths.numel() != B or len(lengths_host) != B or bounds.shape != (B, 2)
+            or frame_ms.shape[0] != B):
+        raise ValueError("trim_bounds: lengths [B], bounds [B, 2], frame_ms [B, ms_stride]")
+    keep, host = _host_i32(lengths_host, B)
+    _lib.call("sat_trim_bounds", _p(wav), _p(lengths), host, B, stride, int(frame_length),
+              int(hop), float(top_db), int(pad_samples), _p(bounds), _p(frame_ms),
+              frame_ms.shape[1], _stream())

@@ -1,5 +1,6 @@
-"""LJSpeech preprocessing: ``preprocess_ljspeech.py`` + ``preprocess/ljspeech.py`` +
-``preprocess/text.py`` without TensorFlow, pyspark or librosa.
+"""LJSpeech and VCTK preprocessing: ``preprocess_ljspeech.py`` + ``preprocess/ljspeech.py``,
+``preprocess_vctk.py`` + ``preprocess/vctk.py`` and ``preprocess/text.py`` without TensorFlow,
+pyspark or librosa.
 
 ``LJSpeech(in_dir, out_dir, hparams)`` reads ``metadata.csv`` (``key|raw|normalised``; the third
 field is the text, the line index the record id) and ``wavs/<key>.wav``, and writes per utterance
@@ -18,8 +19,18 @@ The shipped cleaner is ``basic_cleaners`` (lowercase, collapse whitespace).  The
 ``english_cleaners`` also expands numbers and abbreviations and transliterates to ASCII with
 ``inflect`` / ``unidecode``; that is out of scope here, and the cleaner is an argument.
 
-CLI: ``python -m sat_amd.preprocess ljspeech <in_dir> <out_dir> [--hparam-json-file F]
-[--hparams S] [--source-only | --target-only]``.
+``VCTK(in_dir, out_dir, hparams)`` reads the VCTK 0.8 layout (preprocess/vctk.py:91-127):
+``speaker-info.txt`` (header skipped; id, age, gender with ``F`` -> 0 and anything else -> 1;
+speaker 315 left out), ``wav48/p<id>/*.wav`` and ``txt/p<id>/*.txt`` sorted and paired by key, ids
+in enumeration order.  Each batch is uploaded once, trimmed on the GPU (``Audio.trim_batch``) and
+its mel taken from the trimmed segments in place (``melspectrogram_batch(wav, bounds=...)``).
+Source records carry ``speaker_id, age, gender`` and the first line of the txt file.  An utterance
+whose trimmed length is <= n_fft/2 cannot be framed: it is skipped with a warning and left out of
+``list.csv``.  Both corpora share the batching, the writer thread, the statistics and the two
+output files.
+
+CLI: ``python -m sat_amd.preprocess {ljspeech | vctk} <in_dir> <out_dir> [--hparam-json-file F]
+[--hparams S] [--source-only | --target-only]``; ``vctk`` also takes ``--version 0.8``.
 """
 
 from __future__ import annotations
@@ -30,6 +41,7 @@ import json
 import os
 import queue
 import re
+import sys
 import threading
 from collections import namedtuple
 from typing import Callable, List, Optional, Tuple
@@ -69,6 +81,15 @@ def sequence_to_text(sequence) -> str:
 
 
 class TextAndPath(namedtuple("TextAndPath", ["id", "key", "wav_path", "labels_path", "text"])):
+    pass
+
+
+class SpeakerInfo(namedtuple("SpeakerInfo", ["id", "age", "gender"])):
+    pass
+
+
+class TxtWavRecord(namedtuple("TxtWavRecord",
+                              ["id", "key", "txt_path", "wav_path", "speaker_info"])):
     pass
 
 
@@ -113,7 +134,11 @@ class _Writer:
             raise self._error
 
 
-class LJSpeech:
+class _Corpus:
+    """What the corpora share: length-sorted batches, the writer thread, the statistics,
+    ``hparams.json`` and ``list.csv``.  A corpus lists its records (``_records``; each has ``id``,
+    ``key`` and ``wav_path``), queues one source record (``_put_source``) and turns a batch of
+    loaded waveforms into mels (``_mel_batch``)."""
     BATCH = 32              # utterances per launch
     WINDOW = 8              # batches read ahead and sorted by length together
 
@@ -125,19 +150,19 @@ class LJSpeech:
         self.hparams = hparams
         self.cleaner = cleaner
         self.audio = Audio(hparams, device=device)
+        self.skipped: List[str] = []        # keys _mel_batch left out
 
-    def _extract_text_and_path(self, line, index):
-        parts = line.strip().split('|')
-        key = parts[0]
-        text = parts[2]
-        wav_path = os.path.join(self.in_dir, 'wavs', '%s.wav' % key)
-        return TextAndPath(index, key, wav_path, None, text)
+    def _records(self):
+        raise NotImplementedError("_records")
 
-    def _extract_all_text_and_path(self):
-        with open(os.path.join(self.in_dir, 'metadata.csv'), mode='r', encoding='utf-8') as f:
-            for index, line in enumerate(f):
-                if line.strip():
-                    yield self._extract_text_and_path(line, index)
+    def _put_source(self, writer, r):
+        raise NotImplementedError("_put_source")
+
+    def _mel_batch(self, batch):
+        """``(kept, mel, frames)``: the batch's entries that have a mel, in the row order of
+        ``mel`` [len(kept), F_max, num_mels] and ``frames`` (both on the device)."""
+        mel, frames = self.audio.melspectrogram_batch([w for _, w in batch])
+        return batch, mel, frames
 
     def _text_to_sequence(self, text):
         sequence, clean_text = text_to_sequence(text, self.cleaner)
@@ -153,10 +178,8 @@ class LJSpeech:
         writer = _Writer()
         keys = []
         try:
-            for r in (records if records is not None else self._extract_all_text_and_path()):
-                sequence, clean_text = self._text_to_sequence(r.text)
-                writer.put(tfrecord.write_preprocessed_source_data, r.id, r.key, sequence,
-                           clean_text, self.source_path(r.key))
+            for r in (records if records is not None else self._records()):
+                self._put_source(writer, r)
                 keys.append(r.key)
         finally:
             writer.close()
@@ -182,9 +205,10 @@ class LJSpeech:
         writer = _Writer()
         stats: List[MelStatistics] = []
         try:
-            for batch in self._batches(records if records is not None
-                                       else self._extract_all_text_and_path()):
-                mel, frames = self.audio.melspectrogram_batch([w for _, w in batch])
+            for batch in self._batches(records if records is not None else self._records()):
+                batch, mel, frames = self._mel_batch(batch)
+                if not batch:
+                    continue
                 st = self.audio.mel_statistics(mel, frames).cpu().numpy()
                 mel_h, frames_h = mel.cpu().numpy(), frames.cpu().numpy()
                 for b, (r, _) in enumerate(batch):
@@ -210,10 +234,7 @@ class LJSpeech:
 
     def run(self, process_source: bool = True, process_target: bool = True) -> List[str]:
         os.makedirs(self.out_dir, exist_ok=True)
-        records = list(self._extract_all_text_and_path())
-        keys = [r.key for r in records]
-        if process_source:
-            self.process_sources(records)
+        records = list(self._records())
         if process_target:
             average, stddev, min_db = self.corpus_statistics(self.process_targets(records))
             hp = self.hparams
@@ -229,11 +250,124 @@ class LJSpeech:
             }
             with open(os.path.join(self.out_dir, 'hparams.json'), 'w') as f:
                 json.dump(hparams_obj, f, indent=4)
+        # sources after the targets: an utterance _mel_batch left out gets no record at all
+        records = [r for r in records if r.key not in set(self.skipped)]
+        keys = [r.key for r in records]
+        if process_source:
+            self.process_sources(records)
         with open(os.path.join(self.out_dir, 'list.csv'), 'w', newline='') as csvfile:
             w = csv.writer(csvfile)
             for key in keys:
                 w.writerow([key])
         return keys
+
+
+class LJSpeech(_Corpus):
+    def _extract_text_and_path(self, line, index):
+        parts = line.strip().split('|')
+        key = parts[0]
+        text = parts[2]
+        wav_path = os.path.join(self.in_dir, 'wavs', '%s.wav' % key)
+        return TextAndPath(index, key, wav_path, None, text)
+
+    def _extract_all_text_and_path(self):
+        with open(os.path.join(self.in_dir, 'metadata.csv'), mode='r', encoding='utf-8') as f:
+            for index, line in enumerate(f):
+                if line.strip():
+                    yield self._extract_text_and_path(line, index)
+
+    _records = _extract_all_text_and_path
+
+    def _put_source(self, writer, r):
+        sequence, clean_text = self._text_to_sequence(r.text)
+        writer.put(tfrecord.write_preprocessed_source_data, r.id, r.key, sequence, clean_text,
+                   self.source_path(r.key))
+
+
+class VCTK(_Corpus):
+    """preprocess/vctk.py:83-152, VCTK-Corpus 0.8."""
+
+    def __init__(self, in_dir, out_dir, hparams, speaker_info_filename='speaker-info.txt',
+                 cleaner: Callable[[str], str] = basic_cleaners, device=None,
+                 version: str = "0.8"):
+        if str(version) != "0.8":
+            raise ValueError(f"VCTK version {version}: only the 0.8 layout is read (0.91 needs "
+                             "flite phone labels, which are not built here)")
+        super().__init__(in_dir, out_dir, hparams, cleaner, device)
+        self.speaker_info_filename = speaker_info_filename
+
+    def _load_speaker_info(self):
+        with open(os.path.join(self.in_dir, self.speaker_info_filename), mode='r',
+                  encoding='utf8') as f:
+            for line in f.readlines()[1:]:
+                si = line.split()
+                if not si or si[0] == "315":      # the corpus ships no transcripts for p315
+                    continue
+                yield SpeakerInfo(int(si[0]), int(si[1]), 0 if si[2] == 'F' else 1)
+
+    def list_files(self) -> List[TxtWavRecord]:
+        def files(sub, si, ext):
+            d = os.path.join(self.in_dir, sub, f"p{si.id}")
+            return [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(ext)]
+
+        out: List[TxtWavRecord] = []
+        for si in self._load_speaker_info():
+            txts, wavs = files("txt", si, ".txt"), files("wav48", si, ".wav")
+            if len(txts) != len(wavs):
+                raise ValueError(f"speaker p{si.id}: {len(txts)} txt files, {len(wavs)} wav files")
+            for txt_f, wav_f in zip(txts, wavs):
+                key1 = os.path.splitext(os.path.basename(wav_f))[0]
+                key2 = os.path.splitext(os.path.basename(txt_f))[0]
+                if key1 != key2:
+                    raise ValueError(f"speaker p{si.id}: {wav_f} is paired with {txt_f}")
+                out.append(TxtWavRecord(len(out), key1, txt_f, wav_f, si))
+        return out
+
+    _records = list_files
+
+    def _put_source(self, writer, r):
+        with open(r.txt_path, mode='r', encoding='utf8') as f:
+            txt = f.readline().rstrip("\n")
+        sequence, clean_text = self._text_to_sequence(txt)
+        si = r.speaker_info
+        writer.put(tfrecord.write_preprocessed_vctk_source_data, r.id, r.key, sequence,
+                   clean_text, si.id, si.age, si.gender, self.source_path(r.key))
+
+    def _skip(self, r, why):
+        print(f"warning: skipping {r.key}: {why}", file=sys.stderr)
+        self.skipped.append(r.key)
+
+    def _mel_batch(self, batch):
+        """One upload, the trim launch, one read-back of the bounds, one mel launch over the
+        trimmed segments in place."""
+        import torch
+        n_fft = self.audio._stft_parameters()[0]
+        half_trim = int(self.hparams.trim_frame_length) // 2
+        kept = []
+        for r, w in batch:
+            if len(w) <= half_trim:
+                self._skip(r, f"{len(w)} samples, at most half a trim frame ({half_trim})")
+            else:
+                kept.append((r, w))
+        if not kept:
+            return [], None, None
+        wav, bounds = self.audio.trim_batch([w for _, w in kept])
+        bounds = bounds.cpu().numpy()
+        rows = []
+        for b, (r, _) in enumerate(kept):
+            n = int(bounds[b, 1] - bounds[b, 0])
+            if n <= n_fft // 2:
+                self._skip(r, f"{n} samples after the trim, at most n_fft/2 = {n_fft // 2}: "
+                              "no frame can be formed")
+            else:
+                rows.append(b)
+        if not rows:
+            return [], None, None
+        if len(rows) < len(kept):
+            wav = wav[torch.tensor(rows, device=wav.device)]
+            bounds, kept = bounds[rows], [kept[b] for b in rows]
+        mel, frames = self.audio.melspectrogram_batch(wav, bounds=bounds)
+        return kept, mel, frames
 
 
 def main(argv=None) -> int:
@@ -242,18 +376,24 @@ def main(argv=None) -> int:
                                  description="Waveforms and transcripts to TFRecord training data")
     sub = ap.add_subparsers(dest="dataset", required=True)
     lj = sub.add_parser("ljspeech", help="LJSpeech-1.1 layout: metadata.csv and wavs/")
-    lj.add_argument("in_dir")
-    lj.add_argument("out_dir")
-    lj.add_argument("--hparam-json-file", default=None, help="JSON file of hyper-parameters")
-    lj.add_argument("--hparams", default="", help="ad-hoc overrides, k=v,...")
-    only = lj.add_mutually_exclusive_group()
-    only.add_argument("--source-only", action="store_true")
-    only.add_argument("--target-only", action="store_true")
+    vc = sub.add_parser("vctk", help="VCTK-Corpus 0.8 layout: speaker-info.txt, wav48/, txt/")
+    vc.add_argument("--version", default="0.8", help="corpus version (only 0.8)")
+    for p in (lj, vc):
+        p.add_argument("in_dir")
+        p.add_argument("out_dir")
+        p.add_argument("--hparam-json-file", default=None, help="JSON file of hyper-parameters")
+        p.add_argument("--hparams", default="", help="ad-hoc overrides, k=v,...")
+        only = p.add_mutually_exclusive_group()
+        only.add_argument("--source-only", action="store_true")
+        only.add_argument("--target-only", action="store_true")
     args = ap.parse_args(argv)
     hp = create_hparams(args.hparam_json_file, args.hparams)
     print(hparams_debug_string(hp))
-    LJSpeech(args.in_dir, args.out_dir, hp).run(process_source=not args.target_only,
-                                                 process_target=not args.source_only)
+    if args.dataset == "vctk":
+        corpus = VCTK(args.in_dir, args.out_dir, hp, version=args.version)
+    else:
+        corpus = LJSpeech(args.in_dir, args.out_dir, hp)
+    corpus.run(process_source=not args.target_only, process_target=not args.source_only)
     return 0
 
 

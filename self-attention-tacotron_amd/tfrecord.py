@@ -13,7 +13,11 @@ Restates what the reference's data path reads and writes:
   source (int64 bytes), source_length, text`` and target records ``id, key, mel (float32
   bytes), target_length, mel_width``; parsed as ``parse_preprocessed_source_data`` /
   ``decode_preprocessed_source_data`` (datasets/ljspeech/dataset.py:53-73) and the mel
-  analogues the dataset imports from utils.tfrecord (``PreprocessedMelData``).
+  analogues the dataset imports from utils.tfrecord (``PreprocessedMelData``);
+* the VCTK source record of preprocess/vctk.py:31-44, which adds ``speaker_id, age, gender``, and
+  its parser (datasets/vctk/dataset.py:64-96), which also takes the ``phone, phone_length,
+  phone_txt`` fields of the phone front end when a record carries them (None otherwise).  VCTK
+  target records are the LJSpeech ones.
 """
 
 from __future__ import annotations
@@ -30,6 +34,13 @@ from . import _lib
 
 class PreprocessedSourceData(namedtuple("PreprocessedSourceData",
                                         ["id", "key", "source", "source_length", "text"])):
+    pass
+
+
+class PreprocessedVCTKSourceData(namedtuple("PreprocessedVCTKSourceData",
+                                            ["id", "key", "source", "source_length",
+                                             "speaker_id", "age", "gender", "text", "phone",
+                                             "phone_length", "phone_txt"])):
     pass
 
 
@@ -243,3 +254,51 @@ def parse_preprocessed_mel_data(record: bytes) -> PreprocessedMelData:
                                mel=mel.reshape(-1, width),
                                target_length=_scalar(ex, "target_length", "int64"),
                                mel_width=width)
+
+
+# ---------------------------------------------------------------- VCTK source records
+def vctk_source_example(_id: int, key: str, source: np.ndarray, text: str, speaker_id: int,
+                        age: int, gender: int, phone: np.ndarray = None,
+                        phone_txt: str = None) -> bytes:
+    """preprocess/vctk.py:31-44 (write_preprocessed_source_data's Example); with ``phone`` also
+    the three phone fields datasets/vctk/dataset.py:74-76 reads."""
+    source = np.ascontiguousarray(source, dtype="<i8")
+    feats = {"id": ("int64", [_id]), "key": ("bytes", [key.encode("utf-8")]),
+             "source": ("bytes", [source.tobytes()]),
+             "source_length": ("int64", [len(source)]),
+             "text": ("bytes", [text.encode("utf-8")]),
+             "speaker_id": ("int64", [speaker_id]), "age": ("int64", [age]),
+             "gender": ("int64", [gender])}
+    if phone is not None:
+        phone = np.ascontiguousarray(phone, dtype="<i8")
+        feats.update({"phone": ("bytes", [phone.tobytes()]),
+                      "phone_length": ("int64", [len(phone)]),
+                      "phone_txt": ("bytes", [(phone_txt or "").encode("utf-8")])})
+    return encode_example(feats)
+
+
+def write_preprocessed_vctk_source_data(_id: int, key: str, source: np.ndarray, text: str,
+                                        speaker_id: int, age: int, gender: int,
+                                        filename: str) -> None:
+    write_tfrecords([vctk_source_example(_id, key, source, text, speaker_id, age, gender)],
+                    filename)
+
+
+def parse_preprocessed_vctk_source_data(record: bytes) -> PreprocessedVCTKSourceData:
+    """parse_preprocessed_source_data + decode_preprocessed_source_data
+    (datasets/vctk/dataset.py:64-96).  ``speaker_id``, ``age`` and ``gender`` are required; the
+    phone fields are read when the record has any of them (then all three are required) and are
+    None otherwise."""
+    ex = decode_example(record)
+    phone = phone_length = phone_txt = None
+    if any(n in ex for n in ("phone", "phone_length", "phone_txt")):
+        phone = np.frombuffer(_scalar(ex, "phone", "bytes"), "<i8").astype(np.int64)
+        phone_length = _scalar(ex, "phone_length", "int64")
+        phone_txt = _scalar(ex, "phone_txt", "bytes")
+    return PreprocessedVCTKSourceData(
+        id=_scalar(ex, "id", "int64"), key=_scalar(ex, "key", "bytes"),
+        source=np.frombuffer(_scalar(ex, "source", "bytes"), "<i8").astype(np.int64),
+        source_length=_scalar(ex, "source_length", "int64"),
+        speaker_id=_scalar(ex, "speaker_id", "int64"), age=_scalar(ex, "age", "int64"),
+        gender=_scalar(ex, "gender", "int64"), text=_scalar(ex, "text", "bytes"),
+        phone=phone, phone_length=phone_length, phone_txt=phone_txt)
