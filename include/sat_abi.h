@@ -283,7 +283,9 @@ int sat_gemm_rowdot(int32_t M, int32_t N, int32_t K, const float* A, int64_t lda
                     int64_t ldb, float* C, int64_t ldc, float alpha, float beta, void* stream);
 
 /* ---------------------------------------------------------------- RNG masks
- * Counter-based (Philox-4x32-10) Bernoulli masks: out[i] = (u_i < keep) ? on_value : 0.
+ * Counter-based (Philox-4x32-10) Bernoulli masks: out[i] = (u_i < keep) ? on_value : 0, with
+ * u_i = float(word j = i % 4 of Philox(counter = {i / 4, stream_id}, key = seed)) * 2^-32;
+ * keep >= 1 keeps every element (u_i rounds to 1.0 for the 129 largest words).
  * The per-step seed is read from DEVICE memory (seed_ptr[0]) so a captured graph draws fresh
  * masks on every replay.  Replaces the dropout draws of tf.layers.dropout / tf.nn.dropout
  * (PreNet, ZoneoutLSTMCell, modules/self_attention.py:60). */
@@ -583,7 +585,10 @@ int sat_attn_agent_bwd(const SatAttnAgentBwd* args, void* stream);
  * to be column-summed.  tsplit = k > 1 splits the T steps into k ranges run by separate
  * workgroups (the one-wave-per-position grid otherwise leaves its last residency round almost
  * empty): dK1 / dK2 are then [k][B][N][D] scratch whose slab 0 holds the gradient on return,
- * and pg has k * sat_attn_param_grad_rows(B, N) rows (0 or 1: no split). */
+ * and pg has k * sat_attn_param_grad_rows(B, N) rows (0 or 1: no split).  pg_stride >=
+ * sat_attn_pg_stride(D1, D2, F, KW) (extra columns are written as 0) and <= 4096: the launch
+ * keeps 4 * pg_stride floats of dynamic LDS, refused above the 64 KB launch limit (e.g. D1 =
+ * 448, D2 = 64, F = 8, KW = 7). */
 typedef struct SatAttnParamGrad {
   int32_t T, B, N, D1, D2, F, KW, att1_forward;
   const float* K1; const float* K2;
@@ -929,7 +934,8 @@ int sat_loss_fwd_bwd(const float* mel, const float* tgt, const float* tmask, con
  * Health guard: if any of the n_health int32 words at `health` (device; the step's in-kernel
  * error words) is non-zero the whole update is skipped -- params, moments and *global_step stay
  * as they were -- and status[2] (device, nullable) becomes {skipped steps + 1, first error code}.
- * Lets a replayed training graph refuse garbage without a host sync. */
+ * Lets a replayed training graph refuse garbage without a host sync.
+ * n = 0 is SAT_OK with nothing launched and nothing written (*global_step stays). */
 typedef struct SatAdamConfig {
   float lr0, beta1, beta2, eps, clip_norm;   /* clip_norm <= 0 disables clipping */
   int32_t decay, step_factor;

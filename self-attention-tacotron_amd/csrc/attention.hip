@@ -1324,8 +1324,14 @@ extern "C" int sat_attn_param_grads(const SatAttnParamGrad* a, void* stream) {
   SAT_CHECK_ARG(F == 0 || F == 8 || (F == 5 && (a->D1 + a->D2) <= 256),
                 "sat_attn_param_grads: location features F must be 0, 8 or 5 (D1 + D2 <= 256)");
   SAT_CHECK_ARG(KW * F + F <= 64, "sat_attn_param_grads: location conv needs KW*F + F <= 64");
-  SAT_CHECK_ARG(a->pg_stride >= sat_attn_pg_stride(a->D1, a->D2, F, KW) && a->pg_stride <= 8192,
-                "sat_attn_param_grads: pg stride");
+  SAT_CHECK_ARG(a->pg_stride >= sat_attn_pg_stride(a->D1, a->D2, F, KW),
+                "sat_attn_param_grads: pg stride below sat_attn_pg_stride(D1, D2, F, KW)");
+  // the launch holds one partial row per wave in dynamic LDS: 4 * pg_stride floats, which must
+  // fit the 64 KB a launch gets without a raised function attribute
+  constexpr int64_t kPgLdsLimit = 64 * 1024;
+  SAT_CHECK_ARG(4 * a->pg_stride * (int64_t)sizeof(float) <= kPgLdsLimit,
+                "sat_attn_param_grads: 4 * pg_stride * 4 bytes of dynamic LDS exceed the 64 KB "
+                "launch limit (pg_stride <= 4096)");
   SAT_CHECK_ARG(a->K1 && a->K2 && a->q && a->v1 && a->v2 && a->de1 && a->de2 && a->dK1 &&
                 a->dK2 && a->pg, "sat_attn_param_grads: null pointer");
   SAT_CHECK_ARG(F == 0 || (a->locW && a->loc && a->s_prev && a->df),

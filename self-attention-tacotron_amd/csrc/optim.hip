@@ -168,6 +168,9 @@ extern "C" int sat_adam_step(float* params, const float* grads, float* m, float*
   SAT_CHECK_ARG(n_health >= 0 && n_health <= 256 && (n_health == 0 || health),
                 "sat_adam_step: health words: 0..256 int32 (pointer needed when n_health > 0)");
   SAT_CHECK_ARG(cfg->grad_scale > 0.f, "sat_adam_step: grad_scale must be > 0");
+  // an empty arena: nothing launched, nothing written (global_step, scalars and status included;
+  // the update launch would otherwise ask for a grid of 0 blocks)
+  if (n == 0) return SAT_OK;
   hipStream_t s = as_stream(stream);
   double* part = reinterpret_cast<double*>(workspace);
   int* skip = reinterpret_cast<int*>(part + kNormBlocks);

@@ -29,6 +29,13 @@ __device__ __forceinline__ uint4 philox(uint4 ctr, uint2 key) {
   return ctr;
 }
 
+// u = (float)v * 2^-32 < keep.  (float)v rounds the 129 largest words up to 2^32, so u can be
+// exactly 1.0: keep >= 1 (a rate-0 mask) keeps every element outright instead of dropping those.
+// No draw with keep < 1 is affected.
+__device__ __forceinline__ bool rng_keep(uint32_t v, float keep) {
+  return keep >= 1.f || (float)v * 2.3283064365386963e-10f /* 2^-32 */ < keep;
+}
+
 __global__ void rng_fill_kernel(float* __restrict__ out, int64_t n, const uint64_t* seed_ptr,
                                 uint64_t stream_id, float keep, float on) {
   const uint64_t seed = seed_ptr[0];
@@ -39,11 +46,10 @@ __global__ void rng_fill_kernel(float* __restrict__ out, int64_t n, const uint64
     const uint4 r = philox(make_uint4((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)stream_id,
                                       (uint32_t)(stream_id >> 32)), key);
     const uint32_t v[4] = {r.x, r.y, r.z, r.w};
-    const float inv = 2.3283064365386963e-10f;  // 2^-32
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int64_t i = g * 4 + j;
-      if (i < n) out[i] = ((float)v[j] * inv < keep) ? on : 0.f;
+      if (i < n) out[i] = rng_keep(v[j], keep) ? on : 0.f;
     }
   }
 }
@@ -70,10 +76,9 @@ __global__ void rng_fill_segments_kernel(float* __restrict__ out, const uint64_t
     const uint4 r = philox(make_uint4((uint32_t)gl, (uint32_t)(gl >> 32), (uint32_t)sg.stream_id,
                                       (uint32_t)(sg.stream_id >> 32)), key);
     const uint32_t v[4] = {r.x, r.y, r.z, r.w};
-    const float inv = 2.3283064365386963e-10f;  // 2^-32
     float o[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = ((float)v[j] * inv < sg.keep) ? sg.on_value : 0.f;
+    for (int j = 0; j < 4; ++j) o[j] = rng_keep(v[j], sg.keep) ? sg.on_value : 0.f;
     const int64_t i0 = sg.offset + gl * 4;
     if ((reinterpret_cast<uintptr_t>(out + i0) & 15) == 0 && gl * 4 + 3 < sg.n) {   // one 16-B store
       *reinterpret_cast<float4*>(out + i0) = make_float4(o[0], o[1], o[2], o[3]);

@@ -9,6 +9,7 @@ masks for parity and the backward pass re-uses them without re-drawing.
 Mask values:
 * dropout  ("dropout"): 0 or 1/keep  (inverted dropout, applied by multiplication);
 * zoneout  ("zoneout"): 1 = take the new state, 0 = keep the previous one (keep prob 1-z).
+A rate of 0 (keep = 1) gives a mask with every element on: the generator draws nothing then.
 
 Layouts are batch-major for per-frame dropout and step-major ([T, B, U]) for recurrent state, the
 order the recurrent kernels consume them.
