@@ -9,8 +9,9 @@
 //    (global_load_lds_dwordx4) into a 3-stage ring, counted waits, one raw barrier per K-tile,
 //    fragments of tile k+1 read into a second register set while tile k's last MFMAs run; tile
 //    64/128 x 64/128 and split-K chosen per launch by a cycle model (launch_lds);
-//  * gemm_kernel (register-staged, any strides / modes): BM x BN x 32 tiles, GM x GN waves,
-//    global -> registers -> double-buffered LDS, one barrier per K-tile.
+//  * gemm_kernel (register-staged generic fallback for operands that are not 16-byte loadable):
+//    BM x BN x 32 tiles, 2 x 2 waves, scalar loads of any strides / conv modes -> registers ->
+//    double-buffered LDS, one barrier per K-tile.
 // Weight-gradient products (K = T' * B = 16,000 rows, M x N <= 1024 x 1024) have too few output
 // tiles to fill 256 CUs: they run split-K into an fp32 workspace slab [S][M][N] and a second
 // launch sums the slabs in a fixed order and applies the epilogue (deterministic, no atomics).
@@ -65,7 +66,7 @@ struct GemmP {
   int64_t a_sbatch2, b_sbatch2, c_sbatch2, mul_sbatch2;
   const float* add;
   int64_t add_sm, add_sbatch;
-  int splits, kchunk;          // split-K: grid.z = nb x splits (LDS kernel; the register kernel
+  int splits, kchunk;          // split-K: grid.z = nb x splits (LDS kernel; the generic fallback
                                // splits batch-1 products only), partial slabs in ws
   int nb = 1;                  // batch x batch2 (the split-K reduce walks every batch's slabs)
   float* ws;
@@ -104,11 +105,12 @@ __device__ __forceinline__ int tri_inv(int j) {
   return g;
 }
 
-// Operand loader variants, chosen on the host so the main loop carries no mode branches.
-enum AMode { A_K = 0, A_M = 1, A_IM2COL = 2, A_IM2COLT = 3, A_GEN = 4 };
-enum BMode { B_N = 0, B_K = 1, B_FLIP = 2, B_GEN = 3 };
+// Operand loader variants of gemm_lds_kernel, chosen on the host so its main loop carries no
+// mode branches.
+enum AMode { A_K = 0, A_M = 1, A_IM2COL = 2, A_IM2COLT = 3 };
+enum BMode { B_N = 0, B_K = 1, B_FLIP = 2 };
 
-// generic (scalar) element access, any strides / modes
+// generic fallback: scalar element access, any strides / conv modes (SatGemmDesc a_mode / b_mode)
 __device__ __forceinline__ float load_a(const GemmP& p, const float* A, int m, int k) {
   if (m >= p.M || k >= p.K) return 0.f;
   if (p.a_mode == 0) return A[m * p.a_sm + k * p.a_sk];
@@ -143,18 +145,15 @@ __device__ __forceinline__ float apply_act(float v, int act) {
   }
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
-template <int BM, int BN, int AM, int BMD, int GM = 2, int GN = 2>
-__global__ void __launch_bounds__(64 * GM * GN) gemm_kernel(GemmP p) {
-  constexpr int NT = 64 * GM * GN;                               // GM x GN waves
+// Register-staged generic fallback (operands that are not 16-byte loadable): 2 x 2 waves, one
+// scalar load_a / load_b per element.
+template <int BM, int BN>
+__global__ void __launch_bounds__(256) gemm_kernel(GemmP p) {
+  constexpr int GM = 2, GN = 2, NT = 64 * GM * GN;               // GM x GN waves
   constexpr int WM = BM / GM, WN = BN / GN;
   constexpr int SM = WM / 32, SN = WN / 32;
-  constexpr bool A_MC = (AM == A_M || AM == A_IM2COLT);        // loads run along m
-  constexpr bool B_NC = (BMD == B_N);                          // loads run along n
-  constexpr int PA = A_MC ? 4 : 1, PB = B_NC ? 4 : 1;          // LDS row padding
-  constexpr int NA = (AM == A_GEN) ? BM * BK / NT : BM * BK / (4 * NT);   // per thread
-  constexpr int NB = (BMD == B_GEN) ? BN * BK / NT : BN * BK / (4 * NT);
+  constexpr int PA = 1, PB = 1;                                  // LDS row padding
+  constexpr int NA = BM * BK / NT, NB = BN * BK / NT;            // per thread
   __shared__ __attribute__((aligned(16))) float As[2][BK][BM + PA];
   __shared__ __attribute__((aligned(16))) float Bs[2][BK][BN + PB];
 
@@ -177,148 +176,29 @@ __global__ void __launch_bounds__(64 * GM * GN) gemm_kernel(GemmP p) {
   const int kbeg = split * p.kchunk;
   const int kend = min(p.K, kbeg + p.kchunk);
 
-  // ---- per-thread loader state hoisted out of the K loop
-  const float* arow[NA > 0 ? NA : 1];      // im2col: row base of this thread's output rows
-  int an[NA > 0 ? NA : 1];                 // im2col: position in utterance, -BIG if invalid
-  int aps[NA > 0 ? NA : 1], apn[NA > 0 ? NA : 1];   // im2col-T: (s, n) of the current k
-  if constexpr (AM == A_IM2COL) {
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int gm = m0 + ((tid + i * NT) >> 3);
-      const int s = gm / p.a_L, n = gm - s * p.a_L;
-      arow[i] = A + (int64_t)s * p.a_L * p.a_sm;
-      an[i] = gm < p.M ? n : -(1 << 28);
-    }
-  }
-  if constexpr (AM == A_IM2COLT) {
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int pos = kbeg + (tid + i * NT) / (BM / 4);
-      aps[i] = pos / p.a_L;
-      apn[i] = pos - aps[i] * p.a_L;
-    }
-  }
-  int atap = 0, ac0 = 0;
-  if constexpr (AM == A_IM2COLT) { atap = m0 / p.a_C; ac0 = m0 - atap * p.a_C; }
-
-  float4 ra4[(AM == A_GEN) ? 1 : NA];
-  float ras[(AM == A_GEN) ? NA : 1];
-  float4 rb4[(BMD == B_GEN) ? 1 : NB];
-  float rbs[(BMD == B_GEN) ? NB : 1];
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-
+  float ras[NA], rbs[NB];
   auto fetch = [&](int k0) {
-    if constexpr (AM == A_K) {
 #pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int e = tid + i * NT, m = e >> 3, kq = (e & 7) * 4;
-        const int gm = m0 + m, gk = k0 + kq;
-        ra4[i] = (gm < p.M && gk < kend) ? ld4(A + (int64_t)gm * p.a_sm + gk) : z4;
-      }
-    } else if constexpr (AM == A_M) {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int e = tid + i * NT, k = e / (BM / 4), mq = (e % (BM / 4)) * 4;
-        const int gm = m0 + mq, gk = k0 + k;
-        ra4[i] = (gm < p.M && gk < kend) ? ld4(A + (int64_t)gk * p.a_sk + gm) : z4;
-      }
-    } else if constexpr (AM == A_IM2COL) {
-      const int tap = k0 / p.a_C, c0 = k0 - tap * p.a_C;
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int kq = ((tid + i * NT) & 7) * 4;
-        const int row = an[i] + tap - p.a_shift;
-        const bool ok = row >= 0 && row < p.a_L && k0 + kq < kend;
-        ra4[i] = ok ? ld4(arow[i] + (int64_t)row * p.a_sm + c0 + kq) : z4;
-      }
-    } else if constexpr (AM == A_IM2COLT) {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int e = tid + i * NT, k = e / (BM / 4), mq = (e % (BM / 4)) * 4;
-        const int row = apn[i] + atap - p.a_shift;
-        const bool ok = (k0 + k < kend) && row >= 0 && row < p.a_L && (m0 + mq < p.M);
-        ra4[i] = ok ? ld4(A + (int64_t)(aps[i] * p.a_L + row) * p.a_sm + ac0 + mq) : z4;
-        apn[i] += BK;                                  // next K-tile of this thread
-        while (apn[i] >= p.a_L) { apn[i] -= p.a_L; ++aps[i]; }
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int e = tid + i * NT, m = e / BK, k = e % BK;
-        ras[i] = (k0 + k < kend) ? load_a(p, A, m0 + m, k0 + k) : 0.f;
-      }
+    for (int i = 0; i < NA; ++i) {
+      const int e = tid + i * NT, m = e / BK, k = e % BK;
+      ras[i] = (k0 + k < kend) ? load_a(p, A, m0 + m, k0 + k) : 0.f;
     }
-    if constexpr (BMD == B_N) {
 #pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int e = tid + i * NT, k = e / (BN / 4), nq = (e % (BN / 4)) * 4;
-        const int gk = k0 + k, gn = n0 + nq;
-        rb4[i] = (gk < kend && gn < p.N) ? ld4(B + (int64_t)gk * p.b_sk + gn) : z4;
-      }
-    } else if constexpr (BMD == B_K) {
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int e = tid + i * NT, n = e >> 3, kq = (e & 7) * 4;
-        const int gk = k0 + kq, gn = n0 + n;
-        rb4[i] = (gk < kend && gn < p.N) ? ld4(B + (int64_t)gn * p.b_sn + gk) : z4;
-      }
-    } else if constexpr (BMD == B_FLIP) {
-      const int tap = k0 / p.b_C, o0 = k0 - tap * p.b_C;
-      const float* Wt = B + (int64_t)(p.b_taps - 1 - tap) * p.N * p.b_C + o0;
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int e = tid + i * NT, n = e >> 3, kq = (e & 7) * 4;
-        const int gn = n0 + n;
-        rb4[i] = (gn < p.N && k0 + kq < kend) ? ld4(Wt + (int64_t)gn * p.b_C + kq) : z4;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int e = tid + i * NT, n = e / BK, k = e % BK;
-        rbs[i] = (k0 + k < kend) ? load_b(p, B, k0 + k, n0 + n) : 0.f;
-      }
+    for (int i = 0; i < NB; ++i) {
+      const int e = tid + i * NT, n = e / BK, k = e % BK;
+      rbs[i] = (k0 + k < kend) ? load_b(p, B, k0 + k, n0 + n) : 0.f;
     }
   };
   auto stash = [&](int buf) {
-    if constexpr (AM == A_K || AM == A_IM2COL) {
 #pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int e = tid + i * NT, m = e >> 3, kq = (e & 7) * 4;
-        As[buf][kq + 0][m] = ra4[i].x; As[buf][kq + 1][m] = ra4[i].y;
-        As[buf][kq + 2][m] = ra4[i].z; As[buf][kq + 3][m] = ra4[i].w;
-      }
-    } else if constexpr (AM == A_M || AM == A_IM2COLT) {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int e = tid + i * NT, k = e / (BM / 4), mq = (e % (BM / 4)) * 4;
-        *reinterpret_cast<float4*>(&As[buf][k][mq]) = ra4[i];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int e = tid + i * NT, m = e / BK, k = e % BK;
-        As[buf][k][m] = ras[i];
-      }
+    for (int i = 0; i < NA; ++i) {
+      const int e = tid + i * NT, m = e / BK, k = e % BK;
+      As[buf][k][m] = ras[i];
     }
-    if constexpr (BMD == B_N) {
 #pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int e = tid + i * NT, k = e / (BN / 4), nq = (e % (BN / 4)) * 4;
-        *reinterpret_cast<float4*>(&Bs[buf][k][nq]) = rb4[i];
-      }
-    } else if constexpr (BMD == B_K || BMD == B_FLIP) {
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int e = tid + i * NT, n = e >> 3, kq = (e & 7) * 4;
-        Bs[buf][kq + 0][n] = rb4[i].x; Bs[buf][kq + 1][n] = rb4[i].y;
-        Bs[buf][kq + 2][n] = rb4[i].z; Bs[buf][kq + 3][n] = rb4[i].w;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int e = tid + i * NT, n = e / BK, k = e % BK;
-        Bs[buf][k][n] = rbs[i];
-      }
+    for (int i = 0; i < NB; ++i) {
+      const int e = tid + i * NT, n = e / BK, k = e % BK;
+      Bs[buf][k][n] = rbs[i];
     }
   };
 
@@ -1194,27 +1074,11 @@ extern "C" int sat_gemm_rowdot(int32_t M, int32_t N, int32_t K, const float* A, 
 
 using namespace sat;
 
-template <int BM, int BN, int GM = 2, int GN = 2>
-static hipError_t launch_tiles(int am, int bm, dim3 grid, hipStream_t s, const GemmP& p) {
-#define SAT_GEMM_CASE(A_, B_)                                                               \
-  if (am == A_ && bm == B_) {                                                               \
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, A_, B_, GM, GN>), grid, dim3(64 * GM * GN), 0, s, p);            \
-    return hipGetLastError();                                                               \
-  }
-  SAT_GEMM_CASE(A_K, B_N)
-  SAT_GEMM_CASE(A_K, B_K)
-  SAT_GEMM_CASE(A_M, B_N)
-  SAT_GEMM_CASE(A_M, B_K)
-  SAT_GEMM_CASE(A_IM2COL, B_N)
-  SAT_GEMM_CASE(A_IM2COL, B_FLIP)
-  SAT_GEMM_CASE(A_IM2COLT, B_N)
-#undef SAT_GEMM_CASE
-  hipLaunchKernelGGL((gemm_kernel<BM, BN, A_GEN, B_GEN, GM, GN>), grid, dim3(64 * GM * GN), 0, s, p);
-  return hipGetLastError();
-}
-
 // Tuning hook for probes (tools/probes/gemm_sweep.py): a forced tile / split-K plan for the
-// calling thread's next launches on the LDS kernel (bm = 0 restores the cost model).
+// calling thread's next launches on the LDS kernel (bm = 0 restores the cost model).  A forced
+// plan whose split-K slabs do not fit the descriptor's workspace is not launched: sat_gemm then
+// computes the product on the generic fallback (gemm_kernel), a conv-bank launch reports an
+// error.  Nothing in the product sets a forced plan.
 static thread_local int t_force_bm = 0, t_force_bn = 0, t_force_s = 0, t_probe = 0;
 extern "C" int sat_gemm_probe_mode(int32_t m) {
   SAT_CHECK_ARG(m >= 0 && m <= 3, "sat_gemm_probe_mode: bad mode");
@@ -1430,9 +1294,13 @@ launched:
   return SAT_OK;
 }
 
-// Plan + launch on the LDS-DMA kernel.  Returns 1 (nothing launched) when an operand is not
-// vector-loadable.
-static int launch_lds(const SatGemmDesc* d, GemmP& p, int nb, hipStream_t s) {
+// A route of sat_gemm that does not take the product returns kNextRoute (nothing launched, p as
+// it was); every other value is the product's return code.
+constexpr int kNextRoute = 1;
+
+// The LDS kernel's loader variant of each operand (AMode / BMode), -1 for an operand that is not
+// 16-byte loadable: vector loads need 16-byte aligned rows / batch strides.
+static void classify_operands(const SatGemmDesc* d, const GemmP& p, int* am_out, int* bm_out) {
   const bool astr = (p.a_sbatch % 4 == 0) && (p.a_sbatch2 % 4 == 0) && aligned16(d->A);
   const bool bstr = (p.b_sbatch % 4 == 0) && (p.b_sbatch2 % 4 == 0) && aligned16(d->B);
   int am = -1, bm = -1;
@@ -1450,11 +1318,21 @@ static int launch_lds(const SatGemmDesc* d, GemmP& p, int nb, hipStream_t s) {
   } else {
     if (bstr && d->b_C % BK == 0) bm = B_FLIP;
   }
-  if (am < 0 || bm < 0) return 1;
+  *am_out = am;
+  *bm_out = bm;
+}
+
+// Plan + launch on the LDS-DMA kernel.  Returns kNextRoute when an operand is not
+// vector-loadable, when the pair of loader variants is not instantiated (launch_lds_tiles), or
+// when a forced plan does not fit the split-K scratch: the generic fallback takes those.
+static int launch_lds(const SatGemmDesc* d, GemmP& p, int nb, hipStream_t s) {
+  int am, bm;
+  classify_operands(d, p, &am, &bm);
+  if (am < 0 || bm < 0) return kNextRoute;
   if ((am == A_IM2COL && bm != B_N && bm != B_FLIP) || (am == A_IM2COLT && bm != B_N) ||
       (bm == B_FLIP && am != A_IM2COL))
-    return 1;
-  if (p.cs_out && am == A_M && p.m_real % 4 != 0) return 1;   // the ones chunk must start at m_real
+    return kNextRoute;
+  // (fused column sums: A_M required d->M % 4 == 0, so the ones chunk starts at m_real = d->M)
   // no split-K under a causal hint: the skipped tiles would leave their slab partials stale and
   // the reduce would write them into C above the diagonal
   // (a batched split-K: the reduce's epilogue has no per-batch bias / mul / add)
@@ -1464,7 +1342,7 @@ static int launch_lds(const SatGemmDesc* d, GemmP& p, int nb, hipStream_t s) {
                              am == A_IM2COLT ? d->a_C : 0);
   if (pl.bm == 0)
     pl = plan_lds(p.M, d->N, d->K, nb, split_ok, d->ws_bytes, am == A_IM2COLT ? d->a_C : 0, 0);
-  if (pl.bm == 0) return 1;
+  if (pl.bm == 0) return kNextRoute;   // only a forced plan that does not fit the scratch
   return launch_lds_plan<0>(pl, am, bm, nb, p, s, "sat_gemm");
 }
 
@@ -1509,8 +1387,7 @@ static int gemm_split_segments(const SatGemmDesc* d, void* stream) {
   return sat_gemm(&d2, stream);
 }
 
-extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
-  using namespace sat;
+static int gemm_check_desc(const SatGemmDesc* d) {
   SAT_CHECK_ARG(d != nullptr, "sat_gemm: null descriptor");
   SAT_CHECK_ARG(d->M >= 0 && d->N >= 0 && d->K >= 0 && d->batch >= 1, "sat_gemm: bad sizes");
   SAT_CHECK_ARG(d->a_mode >= 0 && d->a_mode <= 2 && d->b_mode >= 0 && d->b_mode <= 1,
@@ -1519,9 +1396,12 @@ extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
   SAT_CHECK_ARG(d->a_mode == 0 || d->a_C > 0, "sat_gemm: im2col mode needs a_C > 0");
   SAT_CHECK_ARG(d->b_mode != 1 || (d->b_C > 0 && d->b_taps > 0), "sat_gemm: bad conv kernel");
   SAT_CHECK_ARG(d->act >= 0 && d->act <= 4, "sat_gemm: bad activation");
-  if (d->M == 0 || d->N == 0) return SAT_OK;
-  SAT_CHECK_ARG(d->A && d->B && d->C, "sat_gemm: null operand");
-  GemmP p;
+  return SAT_OK;
+}
+
+// The kernels' parameter block of a descriptor (nb = batch x batch2); the routes below add the
+// fields of their own (segments, column sums, split-K).
+static int gemm_fill_params(const SatGemmDesc* d, GemmP& p, int nb) {
   p.M = d->M; p.N = d->N; p.K = d->K;
   p.a_mode = d->a_mode; p.a_L = d->a_L; p.a_C = d->a_C; p.a_shift = d->a_shift;
   p.A = d->A; p.a_sm = d->a_sm; p.a_sk = d->a_sk; p.a_sbatch = d->a_sbatch;
@@ -1543,8 +1423,6 @@ extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
   // operands and the second output block would each see skipped tiles / K-ranges
   SAT_CHECK_ARG(p.tri == 0 || (!d->colsum_out && !d->A2 && !d->B2 && !d->C2),
                 "sat_gemm: tri cannot be combined with colsum_out, A2 / B2 or C2");
-  hipStream_t s = as_stream(stream);
-  const int nb = d->batch * p.batch2;
   p.ws = reinterpret_cast<float*>(d->ws);
   if (d->C2) {
     // two output column blocks: only the LDS kernel's unsplit epilogue takes them
@@ -1554,115 +1432,135 @@ extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
                   "n1 %% 128 == 0");
     p.C2 = d->C2; p.c2_sm = d->c2_sm; p.n1 = d->n1;
   }
+  return SAT_OK;
+}
+
+// Segmented operands (A2 / B2) and / or a second output block (C2): the LDS kernel, or two
+// accumulating launches where the segments cannot run as one reduction.
+static int gemm_route_segments(const SatGemmDesc* d, GemmP& p, int nb, hipStream_t s,
+                               void* stream) {
   if ((d->A2 || d->B2) && !segments_fused_ok(d)) return gemm_split_segments(d, stream);
-  if (d->A2 || d->B2 || d->C2) {
-    if (d->A2 || d->B2) {
-      // two reduction segments: A2 (dense K-contiguous A) and / or B2 (dense B, B's layout)
-      SAT_CHECK_ARG(d->a_mode == 0 && d->b_mode == 0 && !d->colsum_out && d->k1 > 0 &&
-                        d->k1 < d->K && d->k1 % BK == 0 && !t_probe,
-                    "sat_gemm: A2 / B2 need a dense product, 0 < k1 < K, k1 %% 32 == 0, "
-                    "no colsum_out");
-      SAT_CHECK_ARG(!d->A2 || (d->a_sk == 1 && aligned16(d->A2) && d->a2_sm % 4 == 0),
-                    "sat_gemm: A2 needs K-contiguous A and 16-byte aligned A2 rows");
-      SAT_CHECK_ARG(!d->B2 || (aligned16(d->B2) && d->b2_s % 4 == 0 &&
-                               (d->b_sn == 1 || d->b_sk == 1)),
-                    "sat_gemm: B2 needs 16-byte aligned rows / columns");
-      p.A2 = d->A2; p.a2_sm = d->a2_sm; p.k1 = d->k1;
-      p.B2 = d->B2; p.b2_s = d->b2_s;
-    }
-    const int r = launch_lds(d, p, nb, s);
-    if (r == 1 && (d->A2 || d->B2) && !d->C2) return gemm_split_segments(d, stream);
-    SAT_CHECK_ARG(r != 1, "sat_gemm: segmented operands are not vector-loadable");
-    return r;
+  if (!(d->A2 || d->B2 || d->C2)) return kNextRoute;
+  if (d->A2 || d->B2) {
+    // two reduction segments: A2 (dense K-contiguous A) and / or B2 (dense B, B's layout)
+    SAT_CHECK_ARG(d->a_mode == 0 && d->b_mode == 0 && !d->colsum_out && d->k1 > 0 &&
+                      d->k1 < d->K && d->k1 % BK == 0 && !t_probe,
+                  "sat_gemm: A2 / B2 need a dense product, 0 < k1 < K, k1 %% 32 == 0, "
+                  "no colsum_out");
+    SAT_CHECK_ARG(!d->A2 || (d->a_sk == 1 && aligned16(d->A2) && d->a2_sm % 4 == 0),
+                  "sat_gemm: A2 needs K-contiguous A and 16-byte aligned A2 rows");
+    SAT_CHECK_ARG(!d->B2 || (aligned16(d->B2) && d->b2_s % 4 == 0 &&
+                             (d->b_sn == 1 || d->b_sk == 1)),
+                  "sat_gemm: B2 needs 16-byte aligned rows / columns");
+    p.A2 = d->A2; p.a2_sm = d->a2_sm; p.k1 = d->k1;
+    p.B2 = d->B2; p.b2_s = d->b2_s;
   }
-  if (nb == 1 && d->a_mode == 0 && d->b_mode == 0 && !t_probe && d->N == 1 && d->a_sm == 1 &&
-      d->M >= 64 && d->K >= 1024 && !d->bias && d->act == 0 && !d->mul && !d->add && d->ws) {
-    // N == 1 weight gradient (gemm_tn1_kernel): K slices of >= 256 rows, partials reduced by
-    // gemm_splitk_reduce with the usual epilogue (and the fused column sum as row m_real)
-    const int Mx = d->M + (d->colsum_out ? 1 : 0);
-    int S = std::min(64, d->K / 256);
-    while (S > 1 && (int64_t)S * Mx * 4 > d->ws_bytes) --S;
-    if (S > 1) {
-      p.cs_out = d->colsum_out;
-      p.cs_sbatch = 0;
-      p.M = Mx;
-      p.kchunk = ceil_div(d->K, S);
-      p.splits = ceil_div(d->K, p.kchunk);
-      hipLaunchKernelGGL(gemm_tn1_kernel, dim3(ceil_div(Mx, 64), p.splits), dim3(256), 0, s, p);
-      SAT_LAUNCH_CHECK("sat_gemm (N == 1, transposed A)");
-      launch_splitk_reduce(p, s);
-      SAT_LAUNCH_CHECK("sat_gemm (N == 1 reduce)");
-      return SAT_OK;
-    }
-  }
-  if (d->colsum_out) {
-    // C = alpha A B + beta C and colsum_out = alpha 1^T B + beta colsum_out (the bias gradient of
-    // a weight-gradient product) in ONE launch: A gets a row of ones
-    SAT_CHECK_ARG(p.batch2 == 1 && d->a_mode == 0 && d->b_mode == 0 && !d->bias && d->act == 0 &&
-                      !d->mul && !d->add,
-                  "sat_gemm: colsum_out needs a plain product with batch2 == 1 (no bias/act/mul/add)");
-    // bias_sbatch == 0 means "batch 0's sums only", which is right only when every batch reads
-    // the same B; with a batch-strided B the other batches' sums would be dropped silently
-    SAT_CHECK_ARG(nb <= 1 || d->bias_sbatch != 0 || d->b_sbatch == 0,
-                  "sat_gemm: colsum_out of a batched product with a batch-strided B needs "
-                  "bias_sbatch (one [N] row per batch)");
-    {
-      p.cs_out = d->colsum_out;
-      p.cs_sbatch = d->bias_sbatch;     // batch b's sums at colsum_out + b * bias_sbatch
-      p.bias_sbatch = 0;
-      p.M = d->M + 1;
-      const int r = launch_lds(d, p, nb, s);
-      if (r != 1) return r;
-      p.cs_out = nullptr;
-      p.M = d->M;
-    }
-    if (nb > 1) {   // not vector-loadable: one batch-1 product per batch
-      for (int b = 0; b < nb; ++b) {
-        SatGemmDesc d1 = *d;
-        d1.batch = 1;
-        d1.A = d->A + b * d->a_sbatch; d1.B = d->B + b * d->b_sbatch; d1.C = d->C + b * d->c_sbatch;
-        d1.colsum_out = (b > 0 && d->bias_sbatch == 0) ? nullptr : d->colsum_out + b * d->bias_sbatch;
-        d1.a_sbatch = d1.b_sbatch = d1.c_sbatch = d1.bias_sbatch = 0;
-        const int rc = sat_gemm(&d1, stream);
-        if (rc != SAT_OK) return rc;
-      }
-      return SAT_OK;
-    }
-    // operands not vector-loadable: the product, then the column sums as a separate reduction
-    SatGemmDesc d2 = *d;
-    d2.colsum_out = nullptr;
-    const int rc = sat_gemm(&d2, stream);
-    if (rc != SAT_OK) return rc;
-    const int64_t need = sat_workspace_colreduce(d->K, d->N);
-    SAT_CHECK_ARG(d->ws && d->ws_bytes >= need,
-                  "sat_gemm: colsum_out fallback needs ws_bytes >= sat_workspace_colreduce(K, N)");
-    SAT_CHECK_ARG(d->b_sn == 1, "sat_gemm: colsum_out fallback needs B rows contiguous");
-    return colsum_alpha(d->B, d->b_sk, d->K, d->N, d->colsum_out, d->alpha, d->beta, d->ws, s);
-  }
-  if (nb == 1 && d->a_mode == 0 && d->b_mode == 0 && !t_probe && d->M <= kSkinnyM && d->N > 1 &&
-      d->K > 1 && !d->mul && (int64_t)d->M * d->K * 4 + 4 * kSkinnyM * 16 * 4 <= 64 * 1024) {
-    const size_t shm = ((size_t)d->M * d->K + 4 * kSkinnyM * 16) * sizeof(float);
-    hipLaunchKernelGGL(gemm_skinny_kernel, dim3(ceil_div(d->N, 16)), dim3(256), shm, s, p);
-    SAT_LAUNCH_CHECK("sat_gemm (skinny)");
-    return SAT_OK;
-  }
-  if (nb == 1 && d->a_mode == 0 && d->b_mode == 0 && !t_probe &&
-      ((d->N == 1 && d->a_sk == 1) || (d->K == 1 && (int64_t)d->M * d->N < (1LL << 31)))) {
-    if (d->N == 1) {
-      const int vec = (d->K % 4 == 0 && d->a_sm % 4 == 0 && aligned16(d->A)) ? 1 : 0;
-      hipLaunchKernelGGL(gemm_n1_kernel, dim3(ceil_div(d->M, 4)), dim3(256), 0, s, p, vec);
-    } else {
-      const int64_t total = (int64_t)d->M * d->N;
-      hipLaunchKernelGGL(gemm_k1_kernel, dim3((int)std::min<int64_t>((total + 255) / 256, 4096)),
-                         dim3(256), 0, s, p);
-    }
-    SAT_LAUNCH_CHECK("sat_gemm (degenerate shape)");
-    return SAT_OK;
-  }
+  const int r = launch_lds(d, p, nb, s);
+  if (r == kNextRoute && (d->A2 || d->B2) && !d->C2) return gemm_split_segments(d, stream);
+  SAT_CHECK_ARG(r != kNextRoute, "sat_gemm: segmented operands are not vector-loadable");
+  return r;
+}
+
+// N == 1 weight gradient (gemm_tn1_kernel): K slices of >= 256 rows, partials reduced by
+// gemm_splitk_reduce with the usual epilogue (and the fused column sum as row m_real)
+static int gemm_route_tn1(const SatGemmDesc* d, GemmP& p, int nb, hipStream_t s) {
+  if (!(nb == 1 && d->a_mode == 0 && d->b_mode == 0 && !t_probe && d->N == 1 && d->a_sm == 1 &&
+        d->M >= 64 && d->K >= 1024 && !d->bias && d->act == 0 && !d->mul && !d->add && d->ws))
+    return kNextRoute;
+  const int Mx = d->M + (d->colsum_out ? 1 : 0);
+  int S = std::min(64, d->K / 256);
+  while (S > 1 && (int64_t)S * Mx * 4 > d->ws_bytes) --S;
+  if (S <= 1) return kNextRoute;
+  p.cs_out = d->colsum_out;
+  p.cs_sbatch = 0;
+  p.M = Mx;
+  p.kchunk = ceil_div(d->K, S);
+  p.splits = ceil_div(d->K, p.kchunk);
+  hipLaunchKernelGGL(gemm_tn1_kernel, dim3(ceil_div(Mx, 64), p.splits), dim3(256), 0, s, p);
+  SAT_LAUNCH_CHECK("sat_gemm (N == 1, transposed A)");
+  launch_splitk_reduce(p, s);
+  SAT_LAUNCH_CHECK("sat_gemm (N == 1 reduce)");
+  return SAT_OK;
+}
+
+// C = alpha A B + beta C and colsum_out = alpha 1^T B + beta colsum_out (the bias gradient of a
+// weight-gradient product) in ONE launch: A gets a row of ones.  Operands that are not
+// vector-loadable: one batch-1 product per batch, or the product and a separate column reduction.
+static int gemm_route_colsum(const SatGemmDesc* d, GemmP& p, int nb, hipStream_t s,
+                             void* stream) {
+  if (!d->colsum_out) return kNextRoute;
+  SAT_CHECK_ARG(p.batch2 == 1 && d->a_mode == 0 && d->b_mode == 0 && !d->bias && d->act == 0 &&
+                    !d->mul && !d->add,
+                "sat_gemm: colsum_out needs a plain product with batch2 == 1 (no bias/act/mul/add)");
+  // bias_sbatch == 0 means "batch 0's sums only", which is right only when every batch reads
+  // the same B; with a batch-strided B the other batches' sums would be dropped silently
+  SAT_CHECK_ARG(nb <= 1 || d->bias_sbatch != 0 || d->b_sbatch == 0,
+                "sat_gemm: colsum_out of a batched product with a batch-strided B needs "
+                "bias_sbatch (one [N] row per batch)");
   {
+    p.cs_out = d->colsum_out;
+    p.cs_sbatch = d->bias_sbatch;     // batch b's sums at colsum_out + b * bias_sbatch
+    p.bias_sbatch = 0;
+    p.M = d->M + 1;
     const int r = launch_lds(d, p, nb, s);
-    if (r != 1) return r;   // 1: operand layout not vector-loadable, use the register path
+    if (r != kNextRoute) return r;
+    p.cs_out = nullptr;
+    p.M = d->M;
   }
+  if (nb > 1) {   // not vector-loadable: one batch-1 product per batch
+    for (int b = 0; b < nb; ++b) {
+      SatGemmDesc d1 = *d;
+      d1.batch = 1;
+      d1.A = d->A + b * d->a_sbatch; d1.B = d->B + b * d->b_sbatch; d1.C = d->C + b * d->c_sbatch;
+      d1.colsum_out = (b > 0 && d->bias_sbatch == 0) ? nullptr : d->colsum_out + b * d->bias_sbatch;
+      d1.a_sbatch = d1.b_sbatch = d1.c_sbatch = d1.bias_sbatch = 0;
+      const int rc = sat_gemm(&d1, stream);
+      if (rc != SAT_OK) return rc;
+    }
+    return SAT_OK;
+  }
+  // operands not vector-loadable: the product, then the column sums as a separate reduction
+  SatGemmDesc d2 = *d;
+  d2.colsum_out = nullptr;
+  const int rc = sat_gemm(&d2, stream);
+  if (rc != SAT_OK) return rc;
+  const int64_t need = sat_workspace_colreduce(d->K, d->N);
+  SAT_CHECK_ARG(d->ws && d->ws_bytes >= need,
+                "sat_gemm: colsum_out fallback needs ws_bytes >= sat_workspace_colreduce(K, N)");
+  SAT_CHECK_ARG(d->b_sn == 1, "sat_gemm: colsum_out fallback needs B rows contiguous");
+  return colsum_alpha(d->B, d->b_sk, d->K, d->N, d->colsum_out, d->alpha, d->beta, d->ws, s);
+}
+
+// M <= 8 rows (gemm_skinny_kernel)
+static int gemm_route_skinny(const SatGemmDesc* d, const GemmP& p, int nb, hipStream_t s) {
+  if (!(nb == 1 && d->a_mode == 0 && d->b_mode == 0 && !t_probe && d->M <= kSkinnyM && d->N > 1 &&
+        d->K > 1 && !d->mul && (int64_t)d->M * d->K * 4 + 4 * kSkinnyM * 16 * 4 <= 64 * 1024))
+    return kNextRoute;
+  const size_t shm = ((size_t)d->M * d->K + 4 * kSkinnyM * 16) * sizeof(float);
+  hipLaunchKernelGGL(gemm_skinny_kernel, dim3(ceil_div(d->N, 16)), dim3(256), shm, s, p);
+  SAT_LAUNCH_CHECK("sat_gemm (skinny)");
+  return SAT_OK;
+}
+
+// N == 1 with row-contiguous A (gemm_n1_kernel) or K == 1 (gemm_k1_kernel)
+static int gemm_route_degenerate(const SatGemmDesc* d, const GemmP& p, int nb, hipStream_t s) {
+  if (!(nb == 1 && d->a_mode == 0 && d->b_mode == 0 && !t_probe &&
+        ((d->N == 1 && d->a_sk == 1) || (d->K == 1 && (int64_t)d->M * d->N < (1LL << 31)))))
+    return kNextRoute;
+  if (d->N == 1) {
+    const int vec = (d->K % 4 == 0 && d->a_sm % 4 == 0 && aligned16(d->A)) ? 1 : 0;
+    hipLaunchKernelGGL(gemm_n1_kernel, dim3(ceil_div(d->M, 4)), dim3(256), 0, s, p, vec);
+  } else {
+    const int64_t total = (int64_t)d->M * d->N;
+    hipLaunchKernelGGL(gemm_k1_kernel, dim3((int)std::min<int64_t>((total + 255) / 256, 4096)),
+                       dim3(256), 0, s, p);
+  }
+  SAT_LAUNCH_CHECK("sat_gemm (degenerate shape)");
+  return SAT_OK;
+}
+
+// Whatever the LDS kernel did not take, on the generic fallback (gemm_kernel).
+static int gemm_route_generic(const SatGemmDesc* d, GemmP& p, int nb, hipStream_t s) {
   // 128x128 tiles when the output is large, and for long-K weight-gradient products whose
   // output is wide enough (split-K then supplies the workgroups; measured per shape with
   // tools/gemm_census.py: 544x1024x16000 354 -> 262 us, 6144x128x6400 191 -> 136 us, while
@@ -1672,31 +1570,11 @@ extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
   const bool big = ((int64_t)d->M * d->N * nb >= (int64_t)256 * 128 * 128 || wide_dw) &&
                    d->N >= 96 && d->M >= 96;
   const int BMs = big ? 128 : 64;
-  // ---- operand loader variants (vector paths need 16-B aligned rows / batch strides)
-  const bool astr = (p.a_sbatch % 4 == 0) && (p.a_sbatch2 % 4 == 0) && aligned16(d->A);
-  const bool bstr = (p.b_sbatch % 4 == 0) && (p.b_sbatch2 % 4 == 0) && aligned16(d->B);
-  int am = A_GEN, bm = B_GEN;
-  if (d->a_mode == 0) {
-    if (astr && d->a_sk == 1 && d->a_sm % 4 == 0 && d->K % 4 == 0) am = A_K;
-    else if (astr && d->a_sm == 1 && d->a_sk % 4 == 0 && d->M % 4 == 0) am = A_M;
-  } else if (d->a_mode == 1) {
-    if (astr && d->a_sk == 1 && d->a_sm % 4 == 0 && d->a_C % BK == 0) am = A_IM2COL;
-  } else {
-    if (astr && d->a_sk == 1 && d->a_sm % 4 == 0 && d->a_C % BMs == 0) am = A_IM2COLT;
-  }
-  if (d->b_mode == 0) {
-    if (bstr && d->b_sn == 1 && d->b_sk % 4 == 0 && d->N % 4 == 0) bm = B_N;
-    else if (bstr && d->b_sk == 1 && d->b_sn % 4 == 0 && d->K % 4 == 0) bm = B_K;
-  } else {
-    if (bstr && d->b_C % BK == 0) bm = B_FLIP;
-  }
-  if (am == A_GEN || bm == B_GEN) { am = A_GEN; bm = B_GEN; }   // instantiated combinations
   const int gx = ceil_div(d->N, BMs), gy = ceil_div(d->M, BMs);
   const int tiles = gx * gy * nb;
   // split-K for weight-gradient-shaped products (few output tiles, long reduction)
   p.splits = 1;
   p.kchunk = d->K;
-  p.ws = reinterpret_cast<float*>(d->ws);
   if (nb == 1 && tiles < 160 && d->K >= 512 && d->ws != nullptr) {
     int S = std::min<int>(std::max(1, 384 / tiles), std::max(1, d->K / 256));
     S = std::min(S, 64);
@@ -1710,22 +1588,41 @@ extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
   p.remap = (gx * gy >= 16) ? 1 : 0;
   const int gz = p.splits > 1 ? p.splits : nb;
   const dim3 grid(gx, gy, gz);
-  // (a 4x2-wave 128x128 variant, gemm_kernel<128, 128, ., ., 4, 2>, measured 2-15 % slower on
-  // the step's shapes: tile and wave shape are not what limits this kernel)
-  const hipError_t e = big ? launch_tiles<128, 128>(am, bm, grid, s, p)
-                           : launch_tiles<64, 64>(am, bm, grid, s, p);
+  // (2 x 2 waves at both tile sizes: a 4 x 2-wave 128x128 variant measured 2-15 % slower on the
+  // step's shapes; tile and wave shape are not what limits this kernel)
+  if (big) hipLaunchKernelGGL((gemm_kernel<128, 128>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((gemm_kernel<64, 64>), grid, dim3(256), 0, s, p);
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("sat_gemm: launch failed: %s", hipGetErrorString(e));
     return SAT_ERR_HIP;
   }
   if (p.splits > 1) {
-    const int64_t total = (int64_t)d->M * d->N;
-    const int64_t work = (d->N % 4 == 0) ? total / 4 : total;
-    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    hipLaunchKernelGGL(gemm_splitk_reduce, dim3(blocks), dim3(256), 0, s, p);
+    launch_splitk_reduce(p, s);   // one batch: p.nb == 1 and p.M == d->M here
     SAT_LAUNCH_CHECK("sat_gemm(split-k reduce)");
   }
   return SAT_OK;
+}
+
+extern "C" int sat_gemm(const SatGemmDesc* d, void* stream) {
+  using namespace sat;
+  int rc = gemm_check_desc(d);
+  if (rc != SAT_OK) return rc;
+  if (d->M == 0 || d->N == 0) return SAT_OK;
+  SAT_CHECK_ARG(d->A && d->B && d->C, "sat_gemm: null operand");
+  GemmP p;
+  const int nb = d->batch * (d->batch2 > 0 ? d->batch2 : 1);
+  rc = gemm_fill_params(d, p, nb);
+  if (rc != SAT_OK) return rc;
+  hipStream_t s = as_stream(stream);
+  // the routes in order: the first that takes the product launches it
+  if ((rc = gemm_route_segments(d, p, nb, s, stream)) != kNextRoute) return rc;
+  if ((rc = gemm_route_tn1(d, p, nb, s)) != kNextRoute) return rc;
+  if ((rc = gemm_route_colsum(d, p, nb, s, stream)) != kNextRoute) return rc;
+  if ((rc = gemm_route_skinny(d, p, nb, s)) != kNextRoute) return rc;
+  if ((rc = gemm_route_degenerate(d, p, nb, s)) != kNextRoute) return rc;
+  if ((rc = launch_lds(d, p, nb, s)) != kNextRoute) return rc;
+  return gemm_route_generic(d, p, nb, s);
 }
 
 // ---------------------------------------------------------------- CBHG conv bank (one launch

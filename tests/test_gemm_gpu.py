@@ -223,6 +223,79 @@ def test_gemm_lds_forced_plans(cuda, bm, bn, s, M, N, K, ta, tb):
     assert bool((err <= bound).all()), float((err / bound).max())
 
 
+# ---- the generic fallback (gemm_kernel): operands that are not 16-byte loadable, both tile sizes.
+# Bounds: test_gemm_dense's fp32 accumulation bound, c * eps32 * (sum of the magnitudes that are
+# added up) with c * eps32 = 4e-7, against the float64 CPU product.
+@pytest.mark.parametrize("ta,tb", [(False, False), (True, False), (False, True)])
+def test_gemm_generic_big_tile(cuda, ta, tb):
+    """The 128 x 128 generic tile: M N = 2049 x 2051 >= 256 x 128 x 128 selects it, and M, N, K
+    are all odd, so no layout of either operand is vector-loadable; K = 37 leaves a partial
+    second K-tile, M and N a one-row / three-column last tile."""
+    from sat_amd import kernels
+    M, N, K = 2049, 2051, 37
+    g = torch.Generator().manual_seed(M * 7 + N + 2 * ta + tb)
+    A = torch.randn(K, M, generator=g) if ta else torch.randn(M, K, generator=g)
+    B = torch.randn(N, K, generator=g) if tb else torch.randn(K, N, generator=g)
+    bias = torch.randn(N, generator=g)
+    Ad, Bd = A.to(cuda), B.to(cuda)
+    C = kernels.gemm(Ad.t() if ta else Ad, Bd.t() if tb else Bd, bias=bias.to(cuda), act="tanh")
+    Al, Bl = (A.t() if ta else A).double(), (B.t() if tb else B).double()
+    ref = torch.tanh(Al @ Bl + bias.double())
+    bound = 4e-7 * (Al.abs() @ Bl.abs() + bias.double().abs()) + 1e-7
+    err = (C.double().cpu() - ref).abs()
+    assert bool((err <= bound).all()), float((err / bound).max())
+
+
+@pytest.mark.parametrize("ta", [False, True])
+def test_gemm_generic_splitk(cuda, ta):
+    """Split-K on the generic path: 3 x 2 output tiles of 64 x 64, K = 1027 >= 512 and no
+    loadable operand (K odd; transposed A has the row stride M = 130) give S = 4 slabs of 288
+    rows; alpha and beta on a preset C go through the reduce's epilogue (N % 4 != 0: its scalar
+    branch).  The preset C adds |beta| |C0| to the magnitudes of the bound."""
+    from sat_amd import kernels
+    M, N, K = 130, 70, 1027
+    g = torch.Generator().manual_seed(M + 3 * N + K + ta)
+    A = torch.randn(K, M, generator=g) if ta else torch.randn(M, K, generator=g)
+    B = torch.randn(K, N, generator=g)
+    C0 = torch.randn(M, N, generator=g)
+    C = C0.to(cuda)
+    Ad = A.to(cuda)
+    kernels.gemm(Ad.t() if ta else Ad, B.to(cuda), C, alpha=-0.75, beta=2.0)
+    Al = (A.t() if ta else A).double()
+    ref = -0.75 * (Al @ B.double()) + 2.0 * C0.double()
+    bound = 4e-7 * (0.75 * (Al.abs() @ B.double().abs()) + 2.0 * C0.double().abs()) + 1e-7
+    err = (C.double().cpu() - ref).abs()
+    assert bool((err <= bound).all()), float((err / bound).max())
+
+
+def test_gemm_forced_plan_without_scratch_falls_back(cuda, monkeypatch):
+    """A forced split-K plan whose S slabs do not fit the descriptor's workspace (one float short
+    of S M N 4 bytes) is not launched on the LDS kernel: the vector-loadable product runs on the
+    generic fallback, which sizes its own split to the workspace, and is still right."""
+    from sat_amd import _lib, kernels
+    M, N, K, S = 256, 256, 2048, 4
+    g = torch.Generator().manual_seed(M + N + K)
+    A, B = torch.randn(M, K, generator=g), torch.randn(K, N, generator=g)
+    C0 = torch.randn(M, N, generator=g)
+    C = C0.to(cuda)
+
+    def short_ws(d, device):
+        d.ws, d.ws_bytes = kernels._gemm_ws(device).data_ptr(), S * M * N * 4 - 4
+
+    monkeypatch.setattr(kernels, "_with_ws", short_ws)
+    lib = _lib.load()
+    lib.sat_gemm_force_plan(64, 64, S)
+    try:
+        kernels.gemm(A.to(cuda), B.to(cuda), C, alpha=-0.75, beta=2.0)
+        torch.cuda.synchronize()
+    finally:
+        lib.sat_gemm_force_plan(0, 0, 0)
+    ref = -0.75 * (A.double() @ B.double()) + 2.0 * C0.double()
+    bound = 4e-7 * (0.75 * (A.double().abs() @ B.double().abs()) + 2.0 * C0.double().abs()) + 1e-7
+    err = (C.double().cpu() - ref).abs()
+    assert bool((err <= bound).all()), float((err / bound).max())
+
+
 @pytest.mark.parametrize("bm,bn", [(128, 128), (64, 64), (256, 128), (128, 256)])
 def test_conv1d_forced_plans(cuda, bm, bn):
     from sat_amd import _lib, kernels
