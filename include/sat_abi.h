@@ -44,7 +44,10 @@ extern "C" {
  * sat_attn_agent_bwd); 10: SatAttnStep.agent_b_sb, the speaker-vector kernels (sat_rows_bias_fwd /
  * _bwd, sat_ctx_tail_fill); 11: the summary image kernels (sat_image_minmax / sat_image_render);
  * 12: the audio front end (SatMelSpec, sat_melspec, sat_mel_stats); 13: the silence trim
- * (sat_trim_bounds) and SatMelSpec.offsets / offsets_host (a segment of each row). */
+ * (sat_trim_bounds) and SatMelSpec.offsets / offsets_host (a segment of each row).
+ * Still 13 with the vocoder (sat_mel_to_linear, sat_istft, sat_griffin_lim, their scratch queries
+ * and SatGriffinLim): purely additive -- new symbols and one new struct, no existing struct or
+ * signature touched -- so a binding of 13 without them reads a library with them correctly. */
 #define SAT_ABI_VERSION 13
 
 /* ---------------------------------------------------------------- library */
@@ -1081,6 +1084,70 @@ int sat_trim_bounds(const float* wav, const int32_t* lengths, const int32_t* len
                     int32_t B, int32_t wav_stride, int32_t frame_length, int32_t hop, float top_db,
                     int32_t pad_samples, int32_t* bounds, float* frame_ms, int32_t ms_stride,
                     void* stream);
+
+/* ---------------------------------------------------------------- vocoder
+ * Predicted mel -> waveform: what the reference's predict_mel.py:56-62 leaves to an external
+ * WaveNet, done the way Tacotron code bases do it -- denormalise (the inverse of
+ * utils/audio.py:59-60, 72-73), map back to linear magnitudes, Griffin-Lim.  L, F, n_fft, hop, win,
+ * window and twiddle are those of sat_melspec: utterance b has frames[b] frames and
+ * hop * (frames[b] - 1) output samples, whose analysis has frames[b] frames again.  frames (device
+ * int32) is what the kernels read, frames_host the caller's HOST copy, which the entries check (a
+ * device count an entry would have refused makes that utterance all zeros).
+ *   sat_mel_to_linear: mel [B][F_max][M] normalised, average / stddev [M] (device), inv_basis
+ *     [num_freq][M] (the caller's pseudo-inverse of the mel basis): per frame f < frames[b]
+ *     dB = mel * stddev + average + ref_level_db, amp = 10^(dB / 20),
+ *     out[b][f][k] = max(1e-10, sum_m inv_basis[k][m] amp[m]) ^ power (fp64, rounded once); rows
+ *     frames[b] <= f < F_max are written as zeros.  Refused (SAT_ERR_ARGUMENT): a null pointer,
+ *     frames_host[b] outside 0..F_max, power <= 0 or not finite, B > 65535, M > 4096.
+ *   sat_istft: librosa 0.6 istft, the inverse of sat_melspec's analysis.  spec [B][F_max][num_freq]
+ *     complex (re, im pairs, 8-byte aligned).  Per frame the inverse real FFT (the imaginary parts
+ *     of bins 0 and n_fft/2 are ignored) times window, overlap-added at f*hop, divided by the sum
+ *     of the squared window wherever that exceeds FLT_MIN, n_fft/2 samples dropped at each end:
+ *     wav[b][i], i < hop * (frames[b] - 1); the rest of the row up to wav_stride is zero.  Two
+ *     frames share one complex FFT in LDS; the overlap-add is a gather in ascending frame order (no
+ *     atomics: bit-identical runs).  scratch: sat_istft_scratch_bytes(B, F_max, n_fft), 16-byte
+ *     aligned (the windowed frames).
+ *   sat_griffin_lim: angles = exp(i init_phase), prev = 0; n_iter times x = istft(mag * angles),
+ *     reb = stft(x) (reflect padding as sat_melspec), t = reb - momentum / (1 + momentum) * prev,
+ *     prev = reb, angles = t / (|t| + 1e-16); wav = istft(mag * angles).  momentum 0 is the classic
+ *     algorithm, 0.99 librosa's fast variant; n_iter 0 gives istft(mag * exp(i init_phase)).  The
+ *     whole loop is queued on the stream: no synchronisation, nothing read back.  Phases are unit
+ *     phasors throughout.  scratch: sat_griffin_lim_scratch_bytes(B, F_max, n_fft, hop,
+ *     momentum > 0), 16-byte aligned (frames, phasors, prev, the intermediate waveform).
+ *   Both refuse before anything is launched -- SAT_ERR_UNSUPPORTED: n_fft not a power of two in
+ *   64..4096; SAT_ERR_ARGUMENT: win > n_fft, hop < 1, num_freq != n_fft/2 + 1, a null pointer, any
+ *   frames_host[b] > F_max or with hop * (frames_host[b] - 1) <= n_fft/2 (the reflection would
+ *   leave the row), wav_stride below the longest output, scratch too small or misaligned, B > 65535;
+ *   sat_griffin_lim also n_iter < 0 and momentum outside [0, 1) or not finite. */
+typedef struct SatGriffinLim {
+  int32_t B, F_max;
+  int32_t n_fft, hop, win, num_freq;
+  int32_t wav_stride;             /* wav [B][wav_stride] */
+  int32_t n_iter;
+  float momentum;
+  int32_t pad0;
+  const float* mag;               /* [B][F_max][num_freq] linear magnitudes */
+  const float* init_phase;        /* [B][F_max][num_freq] radians */
+  const int32_t* frames;          /* device */
+  const int32_t* frames_host;     /* host */
+  const float* window;
+  const float* twiddle;
+  float* wav;
+  void* scratch;
+  int64_t scratch_bytes;
+} SatGriffinLim;
+int sat_mel_to_linear(const float* mel, const int32_t* frames, const int32_t* frames_host,
+                      int32_t B, int32_t F_max, int32_t M, int32_t num_freq,
+                      const float* inv_basis, const float* average, const float* stddev,
+                      float ref_level_db, float power, float* out, void* stream);
+int64_t sat_istft_scratch_bytes(int32_t B, int32_t F_max, int32_t n_fft);
+int sat_istft(const float* spec, const int32_t* frames, const int32_t* frames_host, int32_t B,
+              int32_t F_max, int32_t n_fft, int32_t hop, int32_t win, int32_t num_freq,
+              const float* window, const float* twiddle, float* wav, int32_t wav_stride,
+              void* scratch, int64_t scratch_bytes, void* stream);
+int64_t sat_griffin_lim_scratch_bytes(int32_t B, int32_t F_max, int32_t n_fft, int32_t hop,
+                                      int32_t momentum_on);
+int sat_griffin_lim(const SatGriffinLim* d, void* stream);
 
 /* ---------------------------------------------------------------- dataset records (host)
  * TFRecord framing of the dataset path: datasets/ljspeech/dataset.py:96-112 reads

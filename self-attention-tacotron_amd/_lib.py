@@ -196,6 +196,11 @@ SatMelSpec = _struct("SatMelSpec", """
     f32:ref_level_db f32:amp_floor ptr:wav ptr:lengths ptr:lengths_host ptr:window ptr:twiddle
     ptr:basis ptr:band_lo ptr:band_hi ptr:out ptr:mag_out ptr:offsets ptr:offsets_host""")
 
+SatGriffinLim = _struct("SatGriffinLim", """
+    i32:B i32:F_max i32:n_fft i32:hop i32:win i32:num_freq i32:wav_stride i32:n_iter
+    f32:momentum i32:pad0 ptr:mag ptr:init_phase ptr:frames ptr:frames_host ptr:window
+    ptr:twiddle ptr:wav ptr:scratch i64:scratch_bytes""")
+
 # name -> argtypes (restype is int for all but sat_last_error_string)
 SIGNATURES = {
     "sat_version": [],
@@ -283,6 +288,9 @@ SIGNATURES.update({
     "sat_melspec": [ctypes.POINTER(SatMelSpec), _P],
     "sat_mel_stats": [_P, _P, _I32, _I32, _I32, _P, _P],
     "sat_trim_bounds": [_P, _P, _P, _I32, _I32, _I32, _I32, _F, _I32, _P, _P, _I32, _P],
+    "sat_mel_to_linear": [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _F, _P, _P],
+    "sat_istft": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _I64, _P],
+    "sat_griffin_lim": [ctypes.POINTER(SatGriffinLim), _P],
 })
 
 RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
@@ -297,6 +305,8 @@ RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
             "sat_decoder_lstms_scratch": (ctypes.c_int64, [_I32]),
             "sat_decode_persistent_scratch_bytes": (ctypes.c_int64, []),
             "sat_decoder_lstms_bwd_scratch": (ctypes.c_int64, [_I32]),
+            "sat_istft_scratch_bytes": (ctypes.c_int64, [_I32, _I32, _I32]),
+            "sat_griffin_lim_scratch_bytes": (ctypes.c_int64, [_I32, _I32, _I32, _I32, _I32]),
             "sat_crc32c": (ctypes.c_uint32, [_P, _I64, ctypes.c_uint32]),
             "sat_tfrecord_masked_crc": (ctypes.c_uint32, [_P, _I64]),
             "sat_tfrecord_frame": (ctypes.c_int64, [_P, _I64, _P]),

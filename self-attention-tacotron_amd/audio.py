@@ -15,6 +15,12 @@ their ``(start, stop)`` bounds; ``melspectrogram_batch(wav, bounds=...)`` then r
 utterance's segment in place, so the VCTK path is one upload, the trim launch, one read-back of
 the bounds (the host needs the lengths and the largest frame count) and one mel launch.
 
+The way back (``csrc/vocoder.hip``) is what a synthesis needs and the reference leaves to an
+external vocoder: ``inv_melspectrogram(_batch)`` = ``denormalize_mel`` and ``_db_to_amp``, the
+pseudo-inverse of the mel basis (``mel_to_linear_batch``) and Griffin-Lim (``griffin_lim_batch``,
+one entry call for the whole loop, built on ``istft_batch``'s kernels).  An utterance of F frames
+comes back as ``hop * (F - 1)`` samples, whose analysis has F frames again.
+
 Not carried over: resampling in ``load_wav`` (a file at another rate raises ``ValueError``).
 """
 
@@ -161,6 +167,32 @@ class Audio:
     def _amp_to_db(self, x):
         return 20 * np.log10(np.maximum(AMP_FLOOR, x))
 
+    def denormalize_mel(self, S):
+        return S * self.stddev_mel_level_db + self.average_mel_level_db
+
+    def _db_to_amp(self, x):
+        return np.power(10.0, x * 0.05)
+
+    def _build_inv_mel_basis(self):
+        """Pseudo-inverse of the float32 mel basis, computed in float64: float32
+        [num_freq, num_mels]."""
+        return np.linalg.pinv(self._mel_basis.astype(np.float64)).astype(np.float32)
+
+    def inv_melspectrogram(self, mel):
+        """Normalised mel [num_mels, frames] (the reference's orientation) -> waveform of
+        ``hop * (frames - 1)`` samples by Griffin-Lim at the defaults of
+        ``inv_melspectrogram_batch``; numpy in, numpy out -- device tensor in, device tensor
+        out."""
+        import torch
+        from . import kernels as K
+        if isinstance(mel, torch.Tensor):
+            rows = K.transpose(mel.contiguous())
+            wav, lengths = self.inv_melspectrogram_batch([rows])
+            return wav[0]
+        rows = np.ascontiguousarray(np.asarray(mel, np.float32).T)
+        wav, lengths = self.inv_melspectrogram_batch([rows])
+        return wav[0].cpu().numpy()
+
     # ------------------------------------------------------------------ the GPU path
     def _dev(self):
         import torch
@@ -286,3 +318,114 @@ class Audio:
         out = torch.empty(mel.shape[0], 4, mel.shape[2], dtype=torch.float64, device=mel.device)
         K.mel_stats(mel, frames, out)
         return out
+
+    # ------------------------------------------------------------------ the vocoder (GPU)
+    def _vocoder_plan(self, device):
+        """``_plan`` plus the tables of the way back: the inverse mel basis and the mel
+        statistics, one value per mel bin."""
+        import torch
+        plan = self._plan(device)
+        if "inv_basis" not in plan:
+            M = self.hparams.num_mels
+            up = lambda a: torch.from_numpy(np.array(a, np.float32)).to(device)
+            plan["inv_basis"] = up(self._build_inv_mel_basis())
+            plan["average"] = up(np.broadcast_to(self.average_mel_level_db, (M,)))
+            plan["stddev"] = up(np.broadcast_to(self.stddev_mel_level_db, (M,)))
+        return plan
+
+    @staticmethod
+    def _frames(frames, B, device):
+        """``(device int32 [B], host list)`` of frame counts given as a list, array or tensor."""
+        import torch
+        host = [int(v) for v in (frames.cpu().numpy() if isinstance(frames, torch.Tensor)
+                                 else np.asarray(frames))]
+        if len(host) != B:
+            raise ValueError(f"frames: {len(host)} entries for {B} utterances")
+        if isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.int32 \
+                and frames.is_contiguous():
+            return frames, host
+        return torch.from_numpy(np.array(host, np.int32)).to(device), host
+
+    def mel_to_linear_batch(self, mel, frames, power: float = 1.5):
+        """Normalised mel [B, F_max, num_mels] on the device -> linear magnitudes
+        [B, F_max, num_freq]: denormalise, dB to amplitude, the inverse mel basis, a floor of
+        1e-10 and ``** power`` (csrc/vocoder.hip).  Rows past ``frames`` are zero."""
+        import torch
+        from . import kernels as K
+        plan = self._vocoder_plan(mel.device)
+        B, F_max, _ = mel.shape
+        dframes, host = self._frames(frames, B, mel.device)
+        out = torch.empty(B, F_max, self.hparams.num_freq, device=mel.device)
+        K.mel_to_linear(mel, dframes, host, inv_basis=plan["inv_basis"], average=plan["average"],
+                        stddev=plan["stddev"], ref_level_db=self.hparams.ref_level_db,
+                        power=power, out=out)
+        return out
+
+    def istft_batch(self, spec, frames):
+        """Complex spectra [B, F_max, num_freq] (complex64, or float32 [.., 2]) on the device ->
+        ``wav [B, hop * (max frames - 1)]``: librosa 0.6 istft, the inverse of the analysis in
+        ``melspectrogram_batch``; samples past ``hop * (frames[b] - 1)`` are zero."""
+        import torch
+        from . import kernels as K
+        n_fft, hop, win = self._stft_parameters()
+        if spec.is_complex():
+            spec = torch.view_as_real(spec.contiguous())
+        plan = self._plan(spec.device)
+        B = spec.shape[0]
+        dframes, host = self._frames(frames, B, spec.device)
+        wav = torch.empty(B, max(hop * (max(host) - 1), 1), device=spec.device)
+        K.istft(spec, dframes, host, n_fft=n_fft, hop=hop, win=win, window=plan["window"],
+                twiddle=plan["twiddle"], wav=wav)
+        return wav
+
+    def griffin_lim_batch(self, mag, frames, n_iter: int = 60, momentum: float = 0.99,
+                          init_phase=None, seed: int = 0):
+        """Linear magnitudes [B, F_max, num_freq] on the device -> ``wav [B, stride]`` by
+        ``n_iter`` Griffin-Lim iterations (``momentum`` 0: the classic algorithm; 0.99: librosa's
+        fast variant), one entry call, nothing read back.  Without ``init_phase`` (radians, the
+        shape of ``mag``) the start phases are uniform in [-pi, pi) from a device generator
+        seeded with ``seed``."""
+        import torch
+        from . import kernels as K
+        n_fft, hop, win = self._stft_parameters()
+        plan = self._plan(mag.device)
+        B = mag.shape[0]
+        dframes, host = self._frames(frames, B, mag.device)
+        if init_phase is None:
+            gen = torch.Generator(device=mag.device)
+            gen.manual_seed(int(seed))
+            init_phase = torch.empty_like(mag).uniform_(-np.pi, np.pi, generator=gen)
+        wav = torch.empty(B, max(hop * (max(host) - 1), 1), device=mag.device)
+        K.griffin_lim(mag, init_phase, dframes, host, n_fft=n_fft, hop=hop, win=win,
+                      window=plan["window"], twiddle=plan["twiddle"], n_iter=n_iter,
+                      momentum=momentum, wav=wav)
+        return wav
+
+    def inv_melspectrogram_batch(self, mels, frames=None, power: float = 1.5, **gl):
+        """Normalised mels as ``predict`` returns them -- a list of [F_b, num_mels] arrays or
+        tensors, or one padded [B, F_max, num_mels] device tensor with ``frames`` -- to
+        ``(wav [B, stride], lengths [B] int32)`` on the device: ``mel_to_linear_batch`` then
+        ``griffin_lim_batch`` (whose options ``gl`` are)."""
+        import torch
+        if isinstance(mels, torch.Tensor) and mels.ndim == 3:
+            if frames is None:
+                raise ValueError("inv_melspectrogram_batch: a padded tensor needs frames")
+            mel = mels.contiguous()
+        else:
+            if len(mels) == 0:
+                raise ValueError("inv_melspectrogram_batch: no mel")
+            on_dev = [isinstance(m, torch.Tensor) for m in mels]
+            device = mels[0].device if on_dev[0] and mels[0].is_cuda else self._dev()
+            frames = [int(m.shape[0]) for m in mels]
+            host = np.zeros((len(mels), max(frames), self.hparams.num_mels), np.float32)
+            for b, m in enumerate(mels):
+                host[b, :frames[b]] = m.cpu().numpy() if on_dev[b] else m
+            mel = torch.from_numpy(host).to(device)
+        # the host list goes on: a device tensor would be read back once per stage
+        dframes, host_frames = self._frames(frames, mel.shape[0], mel.device)
+        hop = self._stft_parameters()[1]
+        mag = self.mel_to_linear_batch(mel, host_frames, power=power)
+        wav = self.griffin_lim_batch(mag, host_frames, **gl)
+        lengths = torch.from_numpy(np.array([hop * (f - 1) for f in host_frames],
+                                            np.int32)).to(mel.device)
+        return wav, lengths

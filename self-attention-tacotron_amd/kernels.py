@@ -1175,3 +1175,83 @@ def trim_bounds(wav, lengths, lengths_host, *, frame_length, hop, top_db, pad_sa
     _lib.call("sat_trim_bounds", _p(wav), _p(lengths), host, B, stride, int(frame_length),
               int(hop), float(top_db), int(pad_samples), _p(bounds), _p(frame_ms),
               frame_ms.shape[1], _stream())
+
+
+# ---- vocoder (csrc/vocoder.hip; sat_amd/audio.py)
+def _contiguous_f32(what, **tensors):
+    for name, t in tensors.items():
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous float32 tensor")
+
+
+def _frames_i32(what, frames, frames_host, B):
+    if frames.dtype != torch.int32 or not frames.is_contiguous() or frames.numel() != B \
+            or len(frames_host) != B:
+        raise ValueError(f"{what}: frames must be a contiguous int32 [B] tensor with its host copy")
+    return _host_i32(frames_host, B)
+
+
+def mel_to_linear(mel, frames, frames_host, *, inv_basis, average, stddev, ref_level_db, power,
+                  out):
+    """Normalised ``mel`` [B, F_max, M] -> linear magnitudes ``out`` [B, F_max, num_freq]
+    (``max(1e-10, inv_basis @ 10^(dB / 20)) ** power``), rows past ``frames`` zero; see
+    include/sat_abi.h.  Only dtypes and buffer sizes are checked here."""
+    _contiguous_f32("mel_to_linear", mel=mel, inv_basis=inv_basis, average=average,
+                    stddev=stddev, out=out)
+    if mel.dim() != 3 or inv_basis.dim() != 2:
+        raise ValueError("mel_to_linear: mel [B, F, M], inv_basis [num_freq, M]")
+    B, F_max, M = mel.shape
+    num_freq = inv_basis.shape[0]
+    if inv_basis.shape[1] != M or average.numel() != M or stddev.numel() != M \
+            or out.shape != (B, F_max, num_freq):
+        raise ValueError("mel_to_linear: inv_basis [num_freq, M], average / stddev [M], "
+                         "out [B, F, num_freq] expected")
+    keep, host = _frames_i32("mel_to_linear", frames, frames_host, B)
+    _lib.call("sat_mel_to_linear", _p(mel), _p(frames), host, B, F_max, M, num_freq,
+              _p(inv_basis), _p(average), _p(stddev), float(ref_level_db), float(power), _p(out),
+              _stream())
+
+
+def istft(spec, frames, frames_host, *, n_fft, hop, win, window, twiddle, wav):
+    """Complex ``spec`` [B, F_max, num_freq, 2] (float32 re / im) -> ``wav`` [B, stride], utterance
+    b in its first ``hop * (frames[b] - 1)`` samples and zeros after; see include/sat_abi.h."""
+    _contiguous_f32("istft", spec=spec, window=window, twiddle=twiddle, wav=wav)
+    if spec.dim() != 4 or spec.shape[3] != 2 or wav.dim() != 2 or wav.shape[0] != spec.shape[0]:
+        raise ValueError("istft: spec [B, F, num_freq, 2], wav [B, stride]")
+    B, F_max, num_freq, _ = spec.shape
+    if window.numel() < n_fft or twiddle.numel() < n_fft:
+        raise ValueError("istft: window and twiddle table need n_fft floats each")
+    keep, host = _frames_i32("istft", frames, frames_host, B)
+    lib = _lib.load()
+    nbytes = int(lib.sat_istft_scratch_bytes(B, F_max, int(n_fft)))
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=spec.device)
+    _lib.call("sat_istft", _p(spec), _p(frames), host, B, F_max, int(n_fft), int(hop), int(win),
+              num_freq, _p(window), _p(twiddle), _p(wav), wav.shape[1], _p(scratch), nbytes,
+              _stream())
+
+
+def griffin_lim(mag, init_phase, frames, frames_host, *, n_fft, hop, win, window, twiddle, n_iter,
+                momentum, wav):
+    """Griffin-Lim on the magnitudes ``mag`` [B, F_max, num_freq] from the start phases
+    ``init_phase`` (radians, same shape) into ``wav`` [B, stride]: the whole loop is queued on the
+    current stream; see include/sat_abi.h."""
+    _contiguous_f32("griffin_lim", mag=mag, init_phase=init_phase, window=window,
+                    twiddle=twiddle, wav=wav)
+    if mag.dim() != 3 or init_phase.shape != mag.shape or wav.dim() != 2 \
+            or wav.shape[0] != mag.shape[0]:
+        raise ValueError("griffin_lim: mag and init_phase [B, F, num_freq], wav [B, stride]")
+    B, F_max, num_freq = mag.shape
+    if window.numel() < n_fft or twiddle.numel() < n_fft:
+        raise ValueError("griffin_lim: window and twiddle table need n_fft floats each")
+    keep, host = _frames_i32("griffin_lim", frames, frames_host, B)
+    lib = _lib.load()
+    nbytes = int(lib.sat_griffin_lim_scratch_bytes(B, F_max, int(n_fft), int(hop),
+                                                   1 if momentum > 0 else 0))
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=mag.device)
+    d = _lib.SatGriffinLim(B=B, F_max=F_max, n_fft=int(n_fft), hop=int(hop), win=int(win),
+                           num_freq=num_freq, wav_stride=wav.shape[1], n_iter=int(n_iter),
+                           momentum=float(momentum), mag=_p(mag), init_phase=_p(init_phase),
+                           frames=_p(frames), frames_host=host, window=_p(window),
+                           twiddle=_p(twiddle), wav=_p(wav), scratch=_p(scratch),
+                           scratch_bytes=nbytes)
+    _lib.check(lib.sat_griffin_lim(ctypes.byref(d), _stream()), "sat_griffin_lim")
