@@ -47,7 +47,8 @@ extern "C" {
  * (sat_trim_bounds) and SatMelSpec.offsets / offsets_host (a segment of each row).
  * Still 13 with the vocoder (sat_mel_to_linear, sat_istft, sat_griffin_lim, their scratch queries
  * and SatGriffinLim): purely additive -- new symbols and one new struct, no existing struct or
- * signature touched -- so a binding of 13 without them reads a library with them correctly. */
+ * signature touched -- so a binding of 13 without them reads a library with them correctly.
+ * Still 13 with the L2 regulariser (sat_l2_regularize, sat_workspace_l2): two new symbols. */
 #define SAT_ABI_VERSION 13
 
 /* ---------------------------------------------------------------- library */
@@ -951,6 +952,25 @@ int sat_adam_step(float* params, const float* grads, float* m, float* v, int64_t
                   int64_t* global_step, float* scalars, void* workspace,
                   const SatAdamConfig* cfg, const int32_t* health, int32_t n_health,
                   int32_t* status, void* stream);
+
+/* L2 regularisation (models/models.py:165-173, modules/regularizers.py) over the flat arenas:
+ *   out[0] = weight * sum over segments of sum_i 0.5 * params[i]^2     (tf.nn.l2_loss per tensor)
+ *   grads[i] += grad_weight * params[i]     for i inside the segments only (grads nullable, or
+ *                                           grad_weight == 0: the loss value alone)
+ *   *loss_total += out[0]                   (nullable; one fp32 add)
+ * seg (DEVICE memory): nseg x {offset, length} in floats, disjoint; the caller has checked on
+ * the host, before uploading it, that every range is non-negative and inside both arenas -- the
+ * kernel trusts the table.  params is never written; gradients outside the segments keep their
+ * bits.  Two launches whatever nseg is: one pass over all segments (fixed grid, each workgroup
+ * walks the table; fp64 partials in a fixed order, no atomics: two runs are bit-identical), one
+ * workgroup that sums the partials.  float4 accesses where a segment's start is 16-byte aligned
+ * in both arenas, scalar otherwise and for the tail.  nseg == 0, or weight == 0 with
+ * grad_weight == 0: out[0] = 0, *loss_total and every gradient untouched.
+ * workspace: sat_workspace_l2() bytes. */
+int64_t sat_workspace_l2(void);
+int sat_l2_regularize(const float* params, float* grads, const int64_t* seg, int32_t nseg,
+                      float weight, float grad_weight, float* out, float* loss_total,
+                      void* workspace, void* stream);
 
 /* Data-parallel exchange (train.py:67,73 MirroredStrategy -> ONE SUM all-reduce per step over
  * [gradients | BN moving statistics | health tail], sat_amd/dp.py).  pack: tail[i] =

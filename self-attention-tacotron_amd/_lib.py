@@ -280,6 +280,7 @@ SIGNATURES.update({
     "sat_global_norm_sq": [_P, _I64, _P, _P],
     "sat_adam_step": [_P, _P, _P, _P, _I64, _P, _P, _P, ctypes.POINTER(SatAdamConfig), _P, _I32,
                       _P, _P],
+    "sat_l2_regularize": [_P, _P, _P, _I32, _F, _F, _P, _P, _P, _P],
     "sat_exchange_pack": [_P, _I32, _P, _I64, _P, _F, _P],
     "sat_exchange_unpack": [_P, _I32, _P, _P],
     "sat_arena_digest": [_P, _I64, _I64, _I32, _P, _P],
@@ -295,6 +296,7 @@ SIGNATURES.update({
 
 RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
             "sat_workspace_adam": (ctypes.c_int64, []),
+            "sat_workspace_l2": (ctypes.c_int64, []),
             "sat_workspace_loss": (ctypes.c_int64, []),
             "sat_mha_scratch_bytes": (ctypes.c_int64, [_I32, _I32, _I32, _I32, _I32]),
             "sat_mha_scratch_bytes_fused": (ctypes.c_int64, [_I32, _I32, _I32, _I32, _I32]),

@@ -122,6 +122,97 @@ __global__ void exchange_unpack_kernel(const float* __restrict__ tail, int n_hea
   if (i < n_health) health[i] = (int)fminf(tail[i], 2147483520.f);
 }
 
+// L2 regularisation (sat_l2_regularize): the arena ranges of the regularised tensors are cut into
+// chunks of kL2Chunk floats, numbered through the table in order; workgroup b takes chunks b,
+// b + grid, ... (a fixed grid, so the partial sums and their order never depend on the data).
+// The table is walked with a cursor that only moves forward -- its index is uniform, so the
+// {offset, length} pairs stay in scalar registers.
+constexpr int kL2Blocks = 1024;
+constexpr int kL2Chunk = 2048;   // 256 threads x 2 float4
+
+__device__ __forceinline__ double sumsq4(const float4 v) {
+  return (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+}
+
+__device__ __forceinline__ float4 fma4(const float a, const float4 w, const float4 g) {
+  return make_float4(fmaf(a, w.x, g.x), fmaf(a, w.y, g.y), fmaf(a, w.z, g.z), fmaf(a, w.w, g.w));
+}
+
+__global__ void __launch_bounds__(256) l2_segments_kernel(const float* __restrict__ p,
+                                                          float* __restrict__ g,
+                                                          const int64_t* __restrict__ seg, int nseg,
+                                                          float gw, double* __restrict__ part) {
+  __shared__ double sh[4];
+  const int t = threadIdx.x;
+  double acc = 0.0;
+  int s = 0;
+  int64_t first = 0;                    // number of segment s's first chunk
+  int64_t off = seg[0], len = seg[1];   // (nseg >= 1: the entry launches nothing otherwise)
+  int64_t nch = (len + kL2Chunk - 1) / kL2Chunk;
+  for (int64_t c = blockIdx.x;; c += gridDim.x) {
+    while (c >= first + nch) {
+      first += nch;
+      if (++s >= nseg) break;
+      off = seg[2 * s];
+      len = seg[2 * s + 1];
+      nch = (len + kL2Chunk - 1) / kL2Chunk;
+    }
+    if (s >= nseg) break;
+    const int64_t e0 = (c - first) * kL2Chunk;
+    const int m = (int)(len - e0 < kL2Chunk ? len - e0 : kL2Chunk);   // floats of this chunk
+    const float* ps = p + off + e0;
+    float* gs = g ? g + off + e0 : nullptr;
+    const bool al = ((reinterpret_cast<uintptr_t>(ps) | reinterpret_cast<uintptr_t>(gs)) & 15) == 0;
+    if (al && m == kL2Chunk) {          // a whole aligned chunk: both loads in flight together
+      const float4 a = reinterpret_cast<const float4*>(ps)[t];
+      const float4 b = reinterpret_cast<const float4*>(ps)[t + 256];
+      if (gs) {
+        float4* g4 = reinterpret_cast<float4*>(gs);
+        const float4 ga = g4[t], gb = g4[t + 256];
+        g4[t] = fma4(gw, a, ga);
+        g4[t + 256] = fma4(gw, b, gb);
+      }
+      acc += sumsq4(a);
+      acc += sumsq4(b);
+      continue;
+    }
+    const int m4 = al ? m >> 2 : 0;
+    for (int i = t; i < m4; i += 256) {
+      const float4 a = reinterpret_cast<const float4*>(ps)[i];
+      if (gs) reinterpret_cast<float4*>(gs)[i] = fma4(gw, a, reinterpret_cast<float4*>(gs)[i]);
+      acc += sumsq4(a);
+    }
+    for (int j = (m4 << 2) + t; j < m; j += 256) {                    // scalar tail / unaligned
+      const float w = ps[j];
+      if (gs) gs[j] = fmaf(gw, w, gs[j]);
+      acc += (double)w * w;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((t & 63) == 0) sh[t >> 6] = acc;
+  __syncthreads();
+  if (t == 0) part[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// out[0] = weight * 0.5 * sum(part) (nparts = 0: 0), *loss_total += out[0]
+__global__ void l2_finish_kernel(const double* __restrict__ part, int nparts, double weight,
+                                 float* __restrict__ out, float* __restrict__ loss_total) {
+  __shared__ double sh[256];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += blockDim.x) acc += part[i];
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float v = (float)(weight * 0.5 * sh[0]);
+    out[0] = v;
+    if (loss_total) loss_total[0] += v;
+  }
+}
+
 }  // namespace
 }  // namespace sat
 
@@ -183,5 +274,34 @@ extern "C" int sat_adam_step(float* params, const float* grads, float* m, float*
   hipLaunchKernelGGL(adam_update_kernel, dim3(blocks), dim3(256), 0, s, params, grads, m, v, n,
                      scalars, cfg->beta1, cfg->beta2, cfg->eps, skip);
   SAT_LAUNCH_CHECK("sat_adam_step");
+  return SAT_OK;
+}
+
+// workspace: the fp64 partials of the segment pass
+extern "C" int64_t sat_workspace_l2(void) { return (int64_t)kL2Blocks * sizeof(double); }
+
+extern "C" int sat_l2_regularize(const float* params, float* grads, const int64_t* seg,
+                                 int32_t nseg, float weight, float grad_weight, float* out,
+                                 float* loss_total, void* workspace, void* stream) {
+  SAT_CHECK_ARG(params && out && workspace, "sat_l2_regularize: null params, out or workspace");
+  SAT_CHECK_ARG(nseg >= 0, "sat_l2_regularize: nseg < 0");
+  SAT_CHECK_ARG(nseg == 0 || seg, "sat_l2_regularize: nseg > 0 needs the segment table");
+  hipStream_t s = as_stream(stream);
+  double* part = reinterpret_cast<double*>(workspace);
+  if (nseg == 0 || (weight == 0.f && grad_weight == 0.f)) {
+    // (a kernel, not a memset node: sat_common.h on memsets under graph replay)
+    hipLaunchKernelGGL(l2_finish_kernel, dim3(1), dim3(256), 0, s, part, 0, 0.0, out,
+                       static_cast<float*>(nullptr));
+    SAT_LAUNCH_CHECK("sat_l2_regularize");
+    return SAT_OK;
+  }
+  hipLaunchKernelGGL(l2_segments_kernel, dim3(kL2Blocks), dim3(256), 0, s, params,
+                     grad_weight != 0.f ? grads : static_cast<float*>(nullptr), seg, (int)nseg,
+                     grad_weight, part);
+  hipLaunchKernelGGL(l2_finish_kernel, dim3(1), dim3(256), 0, s, part, kL2Blocks, (double)weight,
+                     out, loss_total);
+  // one check for both launches (as sat_adam_step does for its three): hipGetLastError returns
+  // the first error since the last check, so a failed first launch is still reported here
+  SAT_LAUNCH_CHECK("sat_l2_regularize");
   return SAT_OK;
 }

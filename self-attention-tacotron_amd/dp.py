@@ -58,6 +58,14 @@ def grad_scale(group=None) -> float:
     return 1.0 / world_size(group)
 
 
+def l2_grad_weight(weight: float, grad_scale: float) -> float:
+    """Factor of the regulariser's gradient added to the SUM-reduced gradient arena: the
+    optimiser uses ``grad_scale * g``, so ``weight / grad_scale`` leaves the effective gradient
+    ``weight * w`` for every world size (exact for a power-of-two world).  The ``grad_weight``
+    of kernels.l2_regularize once the training step calls it."""
+    return float(weight) / float(grad_scale)
+
+
 def allreduce_grads(flat: torch.Tensor, group=None) -> None:
     """SUM all-reduce of the flat gradient arena in place (averaging happens in Adam)."""
     if world_size(group) > 1:

@@ -514,6 +514,34 @@ def rng_fill_segments(base: torch.Tensor, segs, seed_dev: torch.Tensor):
     return base
 
 
+def l2_table(ranges, n_arena: int, device) -> torch.Tensor:
+    """Device table [nseg, 2] int64 of sat_l2_regularize from (offset, length) float ranges,
+    checked here on the host before the upload (the kernel trusts it): every range non-negative,
+    inside an arena of ``n_arena`` floats, sorted and disjoint."""
+    end = 0
+    for off, n in ranges:
+        if off < 0 or n < 0 or off + n > n_arena:
+            raise ValueError(f"l2_table: range ({off}, {n}) is outside an arena of {n_arena} floats")
+        if off < end:
+            raise ValueError(f"l2_table: range ({off}, {n}) overlaps or precedes its predecessor")
+        end = off + n
+    return torch.tensor([[int(o), int(n)] for o, n in ranges], dtype=torch.int64,
+                        device=device).reshape(-1, 2)
+
+
+def l2_regularize(params: torch.Tensor, grads, table: torch.Tensor, weight: float,
+                  grad_weight: float, out: torch.Tensor, loss_total=None) -> torch.Tensor:
+    """sat_l2_regularize: out[0] = weight * sum over the table's ranges of 0.5 * params^2;
+    grads (or None) += grad_weight * params inside the ranges; loss_total[0] (or None) +=
+    out[0].  ``table`` from l2_table for THESE arenas."""
+    assert table.dtype == torch.int64 and table.is_contiguous()
+    assert grads is None or grads.numel() == params.numel()
+    ws = _stream_scratch(params.device, "l2", int(_lib.load().sat_workspace_l2()))
+    _lib.call("sat_l2_regularize", _p(params), _p(grads), _p(table), table.shape[0],
+              float(weight), float(grad_weight), _p(out), _p(loss_total), ws, _stream())
+    return out
+
+
 def seq_mask(x: torch.Tensor, lengths: torch.Tensor, out=None):
     B, N, C = x.shape
     if out is None:

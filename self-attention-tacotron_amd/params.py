@@ -104,7 +104,9 @@ def resolve_dims(hp) -> Dims:
         # (sat_loss_fwd_bwd) computes only that -- refuse rather than silently compute L1
         raise NotImplementedError(f"code_loss_type={hp.code_loss_type!r}: only 'l1' is built")
     if getattr(hp, "use_l2_regularization", False):
-        # models/models.py:164-171 (ext l2_regularization_loss with a name blacklist)
+        # models/models.py:164-171 (ext l2_regularization_loss with a name blacklist): the set
+        # (is_l2_regularized) and the kernel (sat_l2_regularize) exist, the training step does
+        # not call it yet
         raise NotImplementedError("use_l2_regularization=True is not built (off in the configs)")
     if getattr(hp, "speaker_embedd_to_postnet", False):
         raise NotImplementedError("speaker_embedd_to_postnet=True: this model builds no postnet")
@@ -353,6 +355,58 @@ LSTM_SCOPES = ("encoder/cbhg/lstm_fw", "encoder/cbhg/lstm_bw", "decoder/attentio
 
 def is_lstm_param(name: str) -> bool:
     return any(name == f"{s}/kernel" or name == f"{s}/bias" for s in LSTM_SCOPES)
+
+
+def is_l2_regularized(name: str) -> bool:
+    """Whether the reference's ``l2_regularization_loss`` (modules/regularizers.py) sums tensor
+    ``name`` (one of ``param_specs``' names) under ``use_l2_regularization``.
+
+    The reference drops a trainable variable whose TF NAME contains one of "embedding", "bias",
+    "batch_normalization", "output_projection_wrapper/kernel", "lstm_cell",
+    "output_and_stop_token_wrapper/dense/", "output_and_stop_token_wrapper/dense_1/",
+    "stop_token_projection/kernel" (models/models.py:165-168).  The names here are not TF's, so
+    the blacklist is applied to what each tensor is called THERE, not by substring:
+
+    * ``embedding`` and ``speaker_embedding`` (TF: ``embedding``, ``speaker_embedding``): out;
+    * every ``*/bias`` and ``attention_bias`` (TF name contains "bias"): out;
+    * BatchNormalization ``gamma`` / ``beta`` (TF scope ``batch_normalization*``): out;
+    * the five LSTM kernels of ``LSTM_SCOPES`` (TF: ``.../lstm_cell/kernel``, the inner cell of
+      the ZoneoutLSTMCell -- an assumption about TF 1.x naming, DESIGN.md): out;
+    * ``decoder/stop_token_projection/kernel``: out by its own entry;
+    * ``speaker_embedding_projection/kernel``: IN -- in TF it is the model-level unnamed
+      ``tf.layers.Dense`` (models/models.py:72-75), variable ``dense/kernel``, which no entry
+      matches although our name contains "embedding" (the second naming assumption);
+    * every other ``*/kernel`` is in, ``decoder/out_projection/kernel`` included (its TF scope
+      is ``decoder/out_projection``; the ``*_wrapper`` entries match nothing this model builds),
+      and so are the attention vectors ``attention_v`` / ``attention_variable`` (no entry
+      matches ``attention_v`` or ``attention_variable``)."""
+    leaf = name.rsplit("/", 1)[-1]
+    if leaf in ("attention_v", "attention_variable"):
+        return True
+    if leaf != "kernel":
+        return False          # embeddings, biases, attention_bias, BN gamma / beta
+    if is_lstm_param(name) or name == "decoder/stop_token_projection/kernel":
+        return False
+    return True
+
+
+def l2_segments(specs: List[ParamSpec], layout: "Layout") -> List[Tuple[int, int]]:
+    """The arena ranges ``(offset, length)`` in floats of the regularised tensors of ``specs``
+    (``is_l2_regularized``), sorted and disjoint.  Two tensors are merged into one range when
+    they are neighbours in the arena and the first one fills its last 256-byte slot, i.e. no
+    alignment padding lies between them: padding is never inside a range, so it is neither
+    summed nor written."""
+    out: List[Tuple[int, int]] = []
+    for p in sorted((p for p in specs if p.trainable and is_l2_regularized(p.name)),
+                    key=lambda p: layout.offsets[p.name]):
+        off, n = layout.offsets[p.name], int(np.prod(p.shape))
+        if n == 0:
+            continue
+        if out and out[-1][0] + out[-1][1] == off:
+            out[-1] = (out[-1][0], out[-1][1] + n)
+        else:
+            out.append((off, n))
+    return out
 
 
 def to_internal(name: str, a: np.ndarray, row_perm=None) -> np.ndarray:
