@@ -48,7 +48,8 @@ extern "C" {
  * Still 13 with the vocoder (sat_mel_to_linear, sat_istft, sat_griffin_lim, their scratch queries
  * and SatGriffinLim): purely additive -- new symbols and one new struct, no existing struct or
  * signature touched -- so a binding of 13 without them reads a library with them correctly.
- * Still 13 with the L2 regulariser (sat_l2_regularize, sat_workspace_l2): two new symbols. */
+ * Still 13 with the L2 regulariser (sat_l2_regularize, sat_workspace_l2): two new symbols.
+ * Still 13 with the resampler (sat_resample): one new symbol. */
 #define SAT_ABI_VERSION 13
 
 /* ---------------------------------------------------------------- library */
@@ -1104,6 +1105,32 @@ int sat_trim_bounds(const float* wav, const int32_t* lengths, const int32_t* len
                     int32_t B, int32_t wav_stride, int32_t frame_length, int32_t hop, float top_db,
                     int32_t pad_samples, int32_t* bounds, float* frame_ms, int32_t ms_stride,
                     void* stream);
+
+/* ---------------------------------------------------------------- resampling
+ * Audio.load_wav (utils/audio.py:30-31) is librosa.core.load(path, sr=hparams.sample_rate): a file
+ * at another rate is resampled by band-limited interpolation.  For the rate ratio reduced to
+ * L / M (target / original), output n of utterance b lies at input time n M / L:
+ *   out[b][n] = scale * sum over j < taps of
+ *               table[((n M) mod L) * taps + j] * x_b[floor(n M / L) + offset + j]
+ * for n < ceil(lengths[b] L / M), x_b being wav[b] inside [0, lengths[b]) and zero outside (the
+ * halo of an utterance is never read from the neighbouring row); out[b][n] = 0 from there up to
+ * stride_out, so the caller need not clear out.  table [L][taps] (device) is the caller's: phase
+ * p's row holds the windowed sinc at the `taps` input positions an output of that phase reads,
+ * the first of them `offset` (<= 0) samples from floor(n M / L); sat_amd/audio.py
+ * (resample_filter) computes it in fp64 and rounds once.  One launch over
+ * (ceil(stride_out / 256), B); all utterances share the rate pair.  Each output's taps are
+ * summed in an order fixed by `taps` alone (64 interleaved fp32 partial sums by fused
+ * multiply-add, then a butterfly), no atomics: two runs are bit-identical.  lengths (device
+ * int32) is what the kernel reads, lengths_host the caller's HOST copy, which the entry checks
+ * (a device length the entry would have refused makes that row all zeros).
+ * Refused before anything is launched -- SAT_ERR_ARGUMENT: B outside 0..65535, L, M or taps < 1,
+ * a scale that is not finite, a null pointer or one that is not 4-byte aligned (B > 0), any
+ * lengths_host[b] outside 0..stride_in, stride_out < ceil(max lengths_host L / M);
+ * SAT_ERR_UNSUPPORTED: ceil(255 M / L) + taps + 256 floats exceed 64 KB of LDS (a decimation
+ * beyond about 20). */
+int sat_resample(const float* wav, const int32_t* lengths, const int32_t* lengths_host, int32_t B,
+                 int32_t stride_in, const float* table, int32_t L, int32_t M, int32_t taps,
+                 int32_t offset, float scale, float* out, int32_t stride_out, void* stream);
 
 /* ---------------------------------------------------------------- vocoder
  * Predicted mel -> waveform: what the reference's predict_mel.py:56-62 leaves to an external

@@ -289,6 +289,7 @@ SIGNATURES.update({
     "sat_melspec": [ctypes.POINTER(SatMelSpec), _P],
     "sat_mel_stats": [_P, _P, _I32, _I32, _I32, _P, _P],
     "sat_trim_bounds": [_P, _P, _P, _I32, _I32, _I32, _I32, _F, _I32, _P, _P, _I32, _P],
+    "sat_resample": [_P, _P, _P, _I32, _I32, _P, _I32, _I32, _I32, _I32, _F, _P, _I32, _P],
     "sat_mel_to_linear": [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _F, _P, _P],
     "sat_istft": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _I64, _P],
     "sat_griffin_lim": [ctypes.POINTER(SatGriffinLim), _P],

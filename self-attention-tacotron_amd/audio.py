@@ -21,16 +21,95 @@ pseudo-inverse of the mel basis (``mel_to_linear_batch``) and Griffin-Lim (``gri
 one entry call for the whole loop, built on ``istft_batch``'s kernels).  An utterance of F frames
 comes back as ``hop * (F - 1)`` samples, whose analysis has F frames again.
 
-Not carried over: resampling in ``load_wav`` (a file at another rate raises ``ValueError``).
+Resampling (``csrc/resample.hip``) is opt-in.  The reference's ``load_wav`` is
+``librosa.core.load(path, sr=hparams.sample_rate)``, which resamples whatever it reads; here
+``load_wav(path)`` still raises ``ValueError`` on a file at another rate, ``load_wav(path,
+resample=True)`` brings it to ``hparams.sample_rate``, and ``resample_batch`` does so for a list of
+utterances with one upload and one launch per distinct source rate, returning device tensors that
+``trim_batch`` and ``melspectrogram_batch`` take as they are.  The filter is band-limited
+interpolation with a Kaiser-windowed sinc (``resample_filter``): for the ratio reduced to L / M the
+output times have only L distinct fractional parts, so the table holds the exact filter values
+of each phase and nothing is interpolated between its entries.  Its three constants are the ones
+librosa 0.6's default resampler (resampy's ``kaiser_best``) is known by, written from memory:
+neither librosa nor resampy was available when this was built, so equality with their output is
+not pinned.  What is pinned is a float64 evaluation of the same sum straight from the filter
+function and its tone and alias properties (tests/resample_ref.py).
 """
 
 from __future__ import annotations
 
+import math
 import wave
+from collections import namedtuple
 
 import numpy as np
 
 AMP_FLOOR = 1e-5            # utils/audio.py:73
+
+# Kaiser-windowed sinc of the resampler: zero crossings per side, the window's beta, the cut-off
+# as a fraction of the lower Nyquist frequency.  The values resampy's kaiser_best filter (librosa
+# 0.6's default res_type) is known by -- from memory, neither package was at hand to check.
+RESAMPLE_ZEROS = 64
+RESAMPLE_BETA = 14.769656459379492
+RESAMPLE_ROLLOFF = 0.9475937167399596
+RESAMPLE_MAX_PHASES = 1024
+
+ResampleFilter = namedtuple("ResampleFilter", ["table", "L", "M", "taps", "offset"])
+
+
+def resample_ratio(orig: int, target: int):
+    """``target / orig`` reduced to ``(L, M)``: 48000 -> 22050 is (147, 320)."""
+    orig, target = int(orig), int(target)
+    if orig < 1 or target < 1:
+        raise ValueError(f"resample: rates {orig} Hz -> {target} Hz must be positive")
+    g = math.gcd(orig, target)
+    return target // g, orig // g
+
+
+def resampled_length(n: int, L: int, M: int) -> int:
+    """``ceil(n L / M)``: librosa.resample's output length."""
+    return -((-int(n) * int(L)) // int(M))
+
+
+def resample_kernel_function(t):
+    """``h(t) = rolloff sinc(rolloff t) kaiser(t / Z)`` for ``|t| <= Z``, else 0 (float64; t in
+    periods of the lower of the two rates)."""
+    t = np.asarray(t, np.float64)
+    inside = np.abs(t) <= RESAMPLE_ZEROS
+    x = np.where(inside, t / RESAMPLE_ZEROS, 0.0)
+    window = np.i0(RESAMPLE_BETA * np.sqrt(1.0 - x * x)) / np.i0(RESAMPLE_BETA)
+    return np.where(inside, RESAMPLE_ROLLOFF * np.sinc(RESAMPLE_ROLLOFF * t) * window, 0.0)
+
+
+_FILTERS = {}
+
+
+def resample_filter(orig: int, target: int) -> ResampleFilter:
+    """The polyphase table of ``orig`` Hz -> ``target`` Hz: ``(table, L, M, taps, offset)``.
+
+    With ``L / M`` the reduced ratio and ``scale = min(1, L / M)``, output n lies at input time
+    ``n M / L = i0 + p / L`` (``i0 = floor(n M / L)``, phase ``p = (n M) mod L``) and is
+    ``scale * sum_j table[p, j] * x[i0 + offset + j]``: ``table[p, j] = h((p / L - offset - j) *
+    scale)``, ``offset = -ceil(Z / scale)`` and ``taps = 2 ceil(Z / scale) + 2`` cover the support
+    of h for every phase.  The position is formed as one exact integer over ``max(L, M)``, so row
+    p is row L - p reversed bit for bit.  float64 throughout, rounded once to float32 [L, taps]."""
+    key = (int(orig), int(target))
+    f = _FILTERS.get(key)
+    if f is None:
+        L, M = resample_ratio(orig, target)
+        if L > RESAMPLE_MAX_PHASES:
+            raise ValueError(f"resample: {orig} Hz -> {target} Hz reduces to {L}/{M}, a table of "
+                             f"{L} phases (at most {RESAMPLE_MAX_PHASES}): the two rates are not "
+                             "sensibly related")
+        half = -((-RESAMPLE_ZEROS * max(L, M)) // L)        # ceil(Z / scale)
+        taps = 2 * half + 2
+        p = np.arange(L, dtype=np.int64)[:, None]
+        j = np.arange(taps, dtype=np.int64)[None, :]
+        t = (p + (half - j) * L).astype(np.float64) / float(max(L, M))
+        table = resample_kernel_function(t).astype(np.float32)
+        table.setflags(write=False)
+        f = _FILTERS[key] = ResampleFilter(table, L, M, taps, -half)
+    return f
 
 
 def hz_to_mel(f):
@@ -114,13 +193,11 @@ class Audio:
         win_length = int(self.hparams.frame_length_ms / 1000 * self.hparams.sample_rate)
         return n_fft, hop_length, win_length
 
-    def load_wav(self, path):
-        """16-bit PCM through the standard ``wave`` module: float32 in [-1, 1) (``/ 32768``),
-        channels averaged.  No resampling: another rate than hparams.sample_rate is an error."""
+    def _read_wav(self, path, any_rate):
         with wave.open(path, "rb") as f:
             rate, width, channels = f.getframerate(), f.getsampwidth(), f.getnchannels()
             raw = f.readframes(f.getnframes())
-        if rate != self.hparams.sample_rate:
+        if not any_rate and rate != self.hparams.sample_rate:
             raise ValueError(f"{path}: sample rate {rate} Hz, hparams.sample_rate is "
                              f"{self.hparams.sample_rate} Hz (no resampler: convert the file)")
         if width != 2:
@@ -128,6 +205,21 @@ class Audio:
         y = np.frombuffer(raw, "<i2").astype(np.float32) / np.float32(32768.0)
         if channels > 1:
             y = y.reshape(-1, channels).mean(axis=1, dtype=np.float32)
+        return y, rate
+
+    def read_wav(self, path):
+        """``(y, rate)``: ``load_wav``'s reader at whatever rate the file has."""
+        return self._read_wav(path, any_rate=True)
+
+    def load_wav(self, path, resample: bool = False):
+        """16-bit PCM through the standard ``wave`` module: float32 in [-1, 1) (``/ 32768``),
+        channels averaged.  Another rate than hparams.sample_rate is an error, unless
+        ``resample`` asks for the conversion (one utterance through ``resample_batch``: on the
+        GPU; a file already at the rate is returned as read)."""
+        y, rate = self._read_wav(path, any_rate=resample)
+        if rate != self.hparams.sample_rate:
+            out, _ = self.resample_batch([y], rate)
+            return out[0].cpu().numpy()
         return y
 
     def save_wav(self, wav, path):
@@ -243,6 +335,57 @@ class Audio:
                 host[b, :lengths[b]] = w.cpu().numpy() if on_dev[b] else w
             wav = torch.from_numpy(host).to(device)
         return wav, lengths
+
+    def _resample_plan(self, orig, target, device):
+        """``resample_filter``'s table on the device, uploaded once per (orig, target, device)."""
+        import torch
+        key = ("resample", int(orig), int(target), str(device))
+        plan = self._plans.get(key)
+        if plan is None:
+            f = resample_filter(orig, target)
+            plan = self._plans[key] = (f, torch.from_numpy(np.array(f.table)).to(device))
+        return plan
+
+    def resample_batch(self, wavs, rates, target_rate=None):
+        """A list of 1-D waveforms (numpy arrays or tensors) at ``rates`` (one int, or one per
+        utterance) brought to ``target_rate`` (default ``hparams.sample_rate``):
+        ``(list of 1-D device tensors in input order, their lengths)``.  Utterances are grouped by
+        source rate: one padded upload and one launch (csrc/resample.hip) per distinct rate; each
+        result is a view of its group's output rows, ``ceil(len * L / M)`` samples for the ratio
+        reduced to L / M.  An utterance already at the target passes through (uploaded if it is
+        not on the device yet).  Nothing is read back."""
+        import torch
+        from . import kernels as K
+        target = int(self.hparams.sample_rate if target_rate is None else target_rate)
+        if len(wavs) == 0:
+            raise ValueError("resample_batch: no waveform")
+        if isinstance(rates, (int, np.integer)):
+            rates = [int(rates)] * len(wavs)
+        rates = [int(r) for r in rates]
+        if len(rates) != len(wavs):
+            raise ValueError(f"resample_batch: {len(rates)} rates for {len(wavs)} waveforms")
+        out = [None] * len(wavs)
+        for rate in sorted(set(rates)):
+            idx = [i for i, r in enumerate(rates) if r == rate]
+            if rate == target:
+                for i in idx:
+                    w = wavs[i]
+                    if w.ndim != 1:
+                        raise ValueError("resample_batch: waveforms must be 1-D")
+                    if not isinstance(w, torch.Tensor):
+                        w = torch.from_numpy(np.ascontiguousarray(w, np.float32))
+                    out[i] = w if w.is_cuda else w.to(self._dev())
+                continue
+            wav, lengths = self._upload([wavs[i] for i in idx], "resample_batch")
+            f, table = self._resample_plan(rate, target, wav.device)
+            new = [resampled_length(n, f.L, f.M) for n in lengths]
+            dlen = torch.from_numpy(np.array(lengths, np.int32)).to(wav.device)
+            res = torch.empty(len(idx), max(max(new), 1), device=wav.device)
+            K.resample(wav, dlen, lengths, table=table, L=f.L, M=f.M, offset=f.offset,
+                       scale=min(1.0, f.L / f.M), out=res)
+            for b, i in enumerate(idx):
+                out[i] = res[b, :new[b]]
+        return out, [int(w.shape[0]) for w in out]
 
     def trim_batch(self, wavs):
         """A list of 1-D waveforms through one padded upload and the trim launch:

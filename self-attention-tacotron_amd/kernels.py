@@ -1205,6 +1205,27 @@ def trim_bounds(wav, lengths, lengths_host, *, frame_length, hop, top_db, pad_sa
               frame_ms.shape[1], _stream())
 
 
+def resample(wav, lengths, lengths_host, *, table, L, M, offset, scale, out):
+    """Batch of waveforms ``wav`` [B, stride_in] at one rate -> ``out`` [B, stride_out] at
+    ``L / M`` times that rate in one launch: ``table`` [L, taps] holds each phase's filter row,
+    whose first tap lies ``offset`` samples from ``floor(n M / L)``; ``out`` is written whole
+    (zeros past ``ceil(lengths[b] L / M)``); see include/sat_abi.h.  Only dtypes and buffer sizes
+    are checked here: what the entry refuses, it refuses itself."""
+    for name, t in (("wav", wav), ("table", table), ("out", out)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
+            raise ValueError(f"resample: {name} must be a contiguous float32 2-D tensor")
+    if lengths.dtype != torch.int32 or not lengths.is_contiguous():
+        raise ValueError("resample: lengths must be a contiguous int32 tensor")
+    B, stride_in = wav.shape
+    if lengths.numel() != B or len(lengths_host) != B or out.shape[0] != B:
+        raise ValueError("resample: lengths [B] with its host copy, out [B, stride_out]")
+    if table.shape[0] != int(L):
+        raise ValueError(f"resample: table has {table.shape[0]} rows for {L} phases")
+    keep, host = _host_i32(lengths_host, B)
+    _lib.call("sat_resample", _p(wav), _p(lengths), host, B, stride_in, _p(table), int(L), int(M),
+              table.shape[1], int(offset), float(scale), _p(out), out.shape[1], _stream())
+
+
 # ---- vocoder (csrc/vocoder.hip; sat_amd/audio.py)
 def _contiguous_f32(what, **tensors):
     for name, t in tensors.items():

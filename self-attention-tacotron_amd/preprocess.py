@@ -30,7 +30,14 @@ whose trimmed length is <= n_fft/2 cannot be framed: it is skipped with a warnin
 output files.
 
 CLI: ``python -m sat_amd.preprocess {ljspeech | vctk} <in_dir> <out_dir> [--hparam-json-file F]
-[--hparams S] [--source-only | --target-only]``; ``vctk`` also takes ``--version 0.8``.
+[--hparams S] [--source-only | --target-only] [--resample]``; ``vctk`` also takes
+``--version 0.8``.
+
+``--resample`` (``resample=True``) accepts wavs at any rate: ``_batches`` keeps ``(wav, rate)`` as
+read, and ``_mel_batch`` first brings the batch to ``hparams.sample_rate`` on the GPU
+(``Audio.resample_batch``, one launch per distinct source rate); the trim, the mel launch and the
+too-short rule then see the resampled utterances, which stay on the device.  Without it a file at
+another rate raises ``load_wav``'s ``ValueError``, as before.
 """
 
 from __future__ import annotations
@@ -143,13 +150,14 @@ class _Corpus:
     WINDOW = 8              # batches read ahead and sorted by length together
 
     def __init__(self, in_dir, out_dir, hparams, cleaner: Callable[[str], str] = basic_cleaners,
-                 device=None):
+                 device=None, resample: bool = False):
         from .audio import Audio
         self.in_dir = in_dir
         self.out_dir = out_dir
         self.hparams = hparams
         self.cleaner = cleaner
         self.audio = Audio(hparams, device=device)
+        self.resample = resample            # wavs at any rate, brought to hparams.sample_rate
         self.skipped: List[str] = []        # keys _mel_batch left out
 
     def _records(self):
@@ -161,8 +169,19 @@ class _Corpus:
     def _mel_batch(self, batch):
         """``(kept, mel, frames)``: the batch's entries that have a mel, in the row order of
         ``mel`` [len(kept), F_max, num_mels] and ``frames`` (both on the device)."""
+        batch = self._resampled(batch)
         mel, frames = self.audio.melspectrogram_batch([w for _, w in batch])
         return batch, mel, frames
+
+    def _resampled(self, batch):
+        """With ``resample`` the batch's ``(wav, rate)`` entries become device tensors at
+        hparams.sample_rate (``Audio.resample_batch``); without it the batch is returned as it
+        is."""
+        if not self.resample:
+            return batch
+        wavs, _ = self.audio.resample_batch([w for _, (w, _) in batch],
+                                            [rate for _, (_, rate) in batch])
+        return [(r, w) for (r, _), w in zip(batch, wavs)]
 
     def _text_to_sequence(self, text):
         sequence, clean_text = text_to_sequence(text, self.cleaner)
@@ -186,16 +205,22 @@ class _Corpus:
         return keys
 
     def _batches(self, records):
-        """Windows of BATCH * WINDOW utterances, loaded, sorted by length, cut into batches."""
+        """Windows of BATCH * WINDOW utterances, loaded, sorted by length, cut into batches.
+        With ``resample`` an entry's waveform is ``read_wav``'s ``(wav, rate)`` and the order is
+        by duration."""
         window: List[Tuple[TextAndPath, np.ndarray]] = []
+        if self.resample:
+            load, length = self.audio.read_wav, lambda e: len(e[1][0]) / e[1][1]
+        else:
+            load, length = self.audio.load_wav, lambda e: len(e[1])
 
         def flush():
-            window.sort(key=lambda e: len(e[1]))
+            window.sort(key=length)
             for i in range(0, len(window), self.BATCH):
                 yield window[i:i + self.BATCH]
             window.clear()
         for r in records:
-            window.append((r, self.audio.load_wav(r.wav_path)))
+            window.append((r, load(r.wav_path)))
             if len(window) == self.BATCH * self.WINDOW:
                 yield from flush()
         yield from flush()
@@ -289,11 +314,11 @@ class VCTK(_Corpus):
 
     def __init__(self, in_dir, out_dir, hparams, speaker_info_filename='speaker-info.txt',
                  cleaner: Callable[[str], str] = basic_cleaners, device=None,
-                 version: str = "0.8"):
+                 version: str = "0.8", resample: bool = False):
         if str(version) != "0.8":
             raise ValueError(f"VCTK version {version}: only the 0.8 layout is read (0.91 needs "
                              "flite phone labels, which are not built here)")
-        super().__init__(in_dir, out_dir, hparams, cleaner, device)
+        super().__init__(in_dir, out_dir, hparams, cleaner, device, resample)
         self.speaker_info_filename = speaker_info_filename
 
     def _load_speaker_info(self):
@@ -343,6 +368,7 @@ class VCTK(_Corpus):
         import torch
         n_fft = self.audio._stft_parameters()[0]
         half_trim = int(self.hparams.trim_frame_length) // 2
+        batch = self._resampled(batch)
         kept = []
         for r, w in batch:
             if len(w) <= half_trim:
@@ -386,13 +412,17 @@ def main(argv=None) -> int:
         only = p.add_mutually_exclusive_group()
         only.add_argument("--source-only", action="store_true")
         only.add_argument("--target-only", action="store_true")
+        p.add_argument("--resample", action="store_true",
+                       help="bring wavs at another rate to hparams.sample_rate on the GPU "
+                            "(default: such a file is an error)")
     args = ap.parse_args(argv)
     hp = create_hparams(args.hparam_json_file, args.hparams)
     print(hparams_debug_string(hp))
     if args.dataset == "vctk":
-        corpus = VCTK(args.in_dir, args.out_dir, hp, version=args.version)
+        corpus = VCTK(args.in_dir, args.out_dir, hp, version=args.version,
+                      resample=args.resample)
     else:
-        corpus = LJSpeech(args.in_dir, args.out_dir, hp)
+        corpus = LJSpeech(args.in_dir, args.out_dir, hp, resample=args.resample)
     corpus.run(process_source=not args.target_only, process_target=not args.source_only)
     return 0
 
