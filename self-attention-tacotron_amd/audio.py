@@ -312,29 +312,29 @@ class Audio:
             self._plans[key] = plan
         return plan
 
-    def _upload(self, wavs, what):
-        """``(wav [B, stride] on the device, lengths)`` of a list of 1-D waveforms (numpy arrays
-        or tensors): one padded upload."""
+    def _upload(self, rows, what, noun="waveform", ndim=1):
+        """``(padded [B, stride(, C)] on the device, lengths)`` of a list of ``noun`` rows of shape
+        [n] (``ndim`` 1) or [n, C] (2), numpy arrays or tensors: one padded upload."""
         import torch
         from . import kernels as K
-        if len(wavs) == 0:
-            raise ValueError(f"{what}: no waveform")
-        on_dev = [isinstance(w, torch.Tensor) for w in wavs]
-        device = wavs[0].device if on_dev[0] and wavs[0].is_cuda else self._dev()
-        lengths = [int(w.shape[0]) for w in wavs]
-        if any(w.ndim != 1 for w in wavs):
-            raise ValueError(f"{what}: waveforms must be 1-D")
-        B, stride = len(wavs), max(lengths)
+        if len(rows) == 0:
+            raise ValueError(f"{what}: no {noun}")
+        on_dev = [isinstance(r, torch.Tensor) for r in rows]
+        device = rows[0].device if on_dev[0] and rows[0].is_cuda else self._dev()
+        lengths = [int(r.shape[0]) for r in rows]
+        if any(r.ndim != ndim for r in rows):
+            raise ValueError(f"{what}: {noun}s must be {ndim}-D")
+        shape = (len(rows), max(lengths)) + tuple(rows[0].shape[1:])
         if all(on_dev):
-            wav = K.zeros(B, stride, device=device)
-            for b, w in enumerate(wavs):
-                wav[b, :lengths[b]].copy_(w)
+            out = K.zeros(*shape, device=device)
+            for b, r in enumerate(rows):
+                out[b, :lengths[b]].copy_(r)
         else:
-            host = np.zeros((B, stride), np.float32)
-            for b, w in enumerate(wavs):
-                host[b, :lengths[b]] = w.cpu().numpy() if on_dev[b] else w
-            wav = torch.from_numpy(host).to(device)
-        return wav, lengths
+            host = np.zeros(shape, np.float32)
+            for b, r in enumerate(rows):
+                host[b, :lengths[b]] = r.cpu().numpy() if on_dev[b] else r
+            out = torch.from_numpy(host).to(device)
+        return out, lengths
 
     def _resample_plan(self, orig, target, device):
         """``resample_filter``'s table on the device, uploaded once per (orig, target, device)."""
@@ -555,15 +555,7 @@ class Audio:
                 raise ValueError("inv_melspectrogram_batch: a padded tensor needs frames")
             mel = mels.contiguous()
         else:
-            if len(mels) == 0:
-                raise ValueError("inv_melspectrogram_batch: no mel")
-            on_dev = [isinstance(m, torch.Tensor) for m in mels]
-            device = mels[0].device if on_dev[0] and mels[0].is_cuda else self._dev()
-            frames = [int(m.shape[0]) for m in mels]
-            host = np.zeros((len(mels), max(frames), self.hparams.num_mels), np.float32)
-            for b, m in enumerate(mels):
-                host[b, :frames[b]] = m.cpu().numpy() if on_dev[b] else m
-            mel = torch.from_numpy(host).to(device)
+            mel, frames = self._upload(mels, "inv_melspectrogram_batch", "mel", 2)
         # the host list goes on: a device tensor would be read back once per stage
         dframes, host_frames = self._frames(frames, mel.shape[0], mel.device)
         hop = self._stft_parameters()[1]

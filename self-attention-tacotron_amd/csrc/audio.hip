@@ -1,20 +1,16 @@
 // Audio front end: waveform -> log-mel targets (utils/audio.py:51-73 with librosa 0.6 stft
 // semantics) and the per-utterance mel statistics of preprocess/ljspeech.py:119-131.
 //
-// sat_melspec: one workgroup of 256 threads per PAIR of frames of one utterance.  The two windowed
-// frames x0, x1 are the real and imaginary part of one complex n_fft-point FFT z = x0 + i x1 held
-// in LDS (radix-2 decimation in time: the gather from the waveform writes bit-reversed, log2(n_fft)
-// butterfly passes follow); the spectra separate as X0[k] = (Z[k] + conj Z[n-k]) / 2 and
-// X1[k] = (Z[k] - conj Z[n-k]) / 2i, which costs no further twiddle.  Magnitudes replace the
-// twiddle table in LDS, the band sums read them there, and only num_mels floats per frame leave
-// the chip.  LDS per workgroup: 8 n_fft (z) + 4 n_fft + 8 (twiddles, then 2 x (n_fft/2 + 1)
-// magnitudes) = 12 n_fft + 8 bytes: 24 KB at 2048 (6 workgroups per CU), 48 KB at 4096 (3).
+// sat_melspec: one workgroup per PAIR of frames of one utterance, on the STFT core of csrc/stft.h
+// (gather, butterfly passes, separation of the two spectra).  Magnitudes replace the twiddle table
+// in LDS (8 bytes longer), the band sums read them there, and only num_mels floats per frame leave
+// the chip.
 // The separation, the magnitude, the band sum and the logarithm are done in fp64 (a few hundred
 // operations per frame beside the 11 k butterflies), so the FFT's own fp32 rounding is the only
 // error of the result -- DESIGN.md "Audio front end".  With SatMelSpec.offsets an utterance is a
 // segment of its row (the silence trim's bounds, csrc/trim.hip): the row pointer moves by the
 // offset and everything else, the reflection at the segment's ends included, is as before.
-#include "sat_common.h"
+#include "stft.h"
 
 using namespace sat;
 
@@ -29,14 +25,8 @@ struct MelSpecP {
   float ref_level_db, amp_floor;
 };
 
-// sample j of frame f of the utterance reflect-padded by n_fft/2 on both sides, by index on the
-// unpadded row: i = f*hop + j - n_fft/2, mirrored about 0 (i -> -i) or about L-1 (i -> 2(L-1)-i).
-// With n_fft/2 < L and f <= L/hop one mirror always lands inside [0, L).
-__device__ __forceinline__ int reflect_index(int f, int j, int hop, int half_n, int L) {
-  int i = f * hop + j - half_n;
-  if (i < 0) i = -i;
-  if (i >= L) i = 2 * (L - 1) - i;
-  return i;
+__device__ __forceinline__ float magnitude(double re, double im) {
+  return (float)sqrt(re * re + im * im);
 }
 
 __global__ void __launch_bounds__(256) melspec_kernel(MelSpecP p) {
@@ -66,40 +56,14 @@ __global__ void __launch_bounds__(256) melspec_kernel(MelSpecP p) {
   const bool have1 = f1 < frames;
 
   const float* y = p.wav + (int64_t)b * p.wav_stride + off;
-  const int shift = 32 - p.log2n;
-  for (int j = tid; j < n; j += 256) {
-    const float w = p.window[j];
-    float v0 = 0.f, v1 = 0.f;
-    if (w != 0.f) {
-      v0 = w * y[reflect_index(f0, j, p.hop, half_n, L)];
-      if (have1) v1 = w * y[reflect_index(f1, j, p.hop, half_n, L)];
-    }
-    z[__brev((unsigned)j) >> shift] = make_float2(v0, v1);
-  }
-  for (int j = tid; j < half_n; j += 256) tw[j] = p.twiddle[j];
-  __syncthreads();
-
-  for (int s = 0; s < p.log2n; ++s) {
-    const int half = 1 << s, tshift = p.log2n - 1 - s;
-    for (int j = tid; j < half_n; j += 256) {
-      const int pos = j & (half - 1);
-      const int i0 = ((j >> s) << (s + 1)) + pos, i1 = i0 + half;
-      const float2 w = tw[pos << tshift];
-      const float2 a = z[i0], c = z[i1];
-      const float tr = c.x * w.x - c.y * w.y, ti = c.x * w.y + c.y * w.x;
-      z[i0] = make_float2(a.x + tr, a.y + ti);
-      z[i1] = make_float2(a.x - tr, a.y - ti);
-    }
-    __syncthreads();
-  }
+  stft_gather_pair(z, tw, y, L, f0, f1, have1, p.window, p.twiddle, n, p.log2n, p.hop, tid);
+  fft_passes<false>(z, tw, p.log2n, half_n, tid);
 
   // the last pass's barrier also released the twiddles: magnitudes take their place
   for (int k = tid; k < nf; k += 256) {
-    const float2 a = z[k], c = z[(n - k) & (n - 1)];
-    const double r0 = 0.5 * ((double)a.x + c.x), i0 = 0.5 * ((double)a.y - c.y);
-    const double r1 = 0.5 * ((double)a.y + c.y), i1 = 0.5 * ((double)c.x - a.x);
-    const float m0 = (float)sqrt(r0 * r0 + i0 * i0);
-    const float m1 = have1 ? (float)sqrt(r1 * r1 + i1 * i1) : 0.f;
+    const BinPair x = separate_bin(z, k, n);
+    const float m0 = magnitude(x.r0(), x.i0());
+    const float m1 = have1 ? magnitude(x.r1(), x.i1()) : 0.f;
     mag[k] = m0;
     mag[nf + k] = m1;
     if (mag0) {
@@ -174,14 +138,7 @@ __global__ void __launch_bounds__(256) mel_stats_kernel(MelStatsP p) {
 extern "C" int sat_melspec(const SatMelSpec* d, void* stream) {
   SAT_CHECK_ARG(d, "sat_melspec: null descriptor");
   const int n = d->n_fft;
-  if (n < 64 || n > 4096 || (n & (n - 1)) != 0) {
-    set_error("sat_melspec: n_fft %d is not a power of two in 64..4096", n);
-    return SAT_ERR_UNSUPPORTED;
-  }
-  SAT_CHECK_ARG(d->win >= 1 && d->win <= n, "sat_melspec: win %d outside 1..n_fft %d", d->win, n);
-  SAT_CHECK_ARG(d->hop >= 1, "sat_melspec: hop %d < 1", d->hop);
-  SAT_CHECK_ARG(d->num_freq == n / 2 + 1, "sat_melspec: num_freq %d != n_fft/2 + 1 = %d",
-                d->num_freq, n / 2 + 1);
+  if (const int rc = check_stft_config("sat_melspec", n, d->hop, d->win, d->num_freq)) return rc;
   SAT_CHECK_ARG(d->B >= 0 && d->B <= 65535 && d->num_mels >= 1 && d->wav_stride >= 0 &&
                 d->F_max >= 0, "sat_melspec: bad sizes");
   if (d->B == 0) return SAT_OK;
@@ -207,14 +164,12 @@ extern "C" int sat_melspec(const SatMelSpec* d, void* stream) {
   }
   SAT_CHECK_ARG(d->F_max >= max_frames, "sat_melspec: F_max %d < the largest frame count %d",
                 d->F_max, max_frames);
-  int log2n = 0;
-  while ((1 << log2n) < n) ++log2n;
   MelSpecP p{d->wav, d->lengths, d->offsets, d->window, reinterpret_cast<const float2*>(d->twiddle), d->basis,
-             d->band_lo, d->band_hi, d->out, d->mag_out, d->B, d->wav_stride, n, log2n, d->hop,
+             d->band_lo, d->band_hi, d->out, d->mag_out, d->B, d->wav_stride, n, ilog2(n), d->hop,
              d->num_mels, d->num_freq, d->F_max, d->ref_level_db, d->amp_floor};
-  const size_t lds = (size_t)12 * n + 8;
-  hipLaunchKernelGGL(melspec_kernel, dim3((d->F_max + 1) / 2, d->B), dim3(256), lds,
-                     as_stream(stream), p);
+  // + 8: 2 x (n/2 + 1) magnitudes take the place of the n/2 float2 twiddles
+  hipLaunchKernelGGL(melspec_kernel, dim3((d->F_max + 1) / 2, d->B), dim3(256),
+                     stft_lds_bytes(n) + 8, as_stream(stream), p);
   SAT_LAUNCH_CHECK("sat_melspec");
   return SAT_OK;
 }

@@ -38,6 +38,7 @@ __device__ __forceinline__ int trim_frames(const TrimP& p, int L) {
 }
 
 // sample i of the padded utterance (i counted from the first padding sample), squared
+// (not stft.h's reflect_index: a 64-bit index about the trim's own half-width; keep it apart)
 __device__ __forceinline__ float padded_square(const float* y, int64_t i, int half, int L) {
   i -= half;
   if (i < 0) i = -i;

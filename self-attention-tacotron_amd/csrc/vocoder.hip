@@ -1,23 +1,20 @@
 // Vocoder: normalised mel -> linear magnitudes -> waveform by Griffin-Lim, the inverse of the audio
-// front end (csrc/audio.hip) with the same conventions: librosa 0.6 stft / istft semantics, the
-// padded periodic Hann window, the (cos, -sin) twiddle table, radix-2 decimation in time in LDS.
+// front end (csrc/audio.hip) on the same STFT core (csrc/stft.h: conventions, FFT in LDS, size).
 //
 // sat_mel_to_linear: one workgroup per frame; the frame's num_mels amplitudes 10^(dB / 20) go to
 //   LDS as doubles, thread k forms lin[k] = max(1e-10, inv_basis[k] . amp)^power in fp64.
 // sat_istft: the two launches every synthesis step is made of --
 //   inverse_kernel, one workgroup of 256 threads per PAIR of frames: the two half spectra X0, X1
 //     are extended by conjugate symmetry and combined as Z = X0 + i X1, one complex inverse FFT
-//     (the forward table with its sine negated) gives frame 0 in the real and frame 1 in the
-//     imaginary part; times window / n_fft they go to the frame buffer, and only over the window's
-//     support [(n_fft - win) / 2, + win): the zero-padded rest of a frame adds nothing.
-//     LDS: 8 n_fft (z) + 4 n_fft (twiddles) = 12 n_fft bytes, 24 KB at 2048 (6 workgroups per CU of
-//     160 KB), 48 KB at 4096 (3), as the analysis kernel.
+//     gives frame 0 in the real and frame 1 in the imaginary part; times window / n_fft they go to
+//     the frame buffer, and only over the window's support [(n_fft - win) / 2, + win): the
+//     zero-padded rest of a frame adds nothing.
 //   overlap_add_kernel, one thread per output sample: a GATHER over the few frames whose window
 //     support covers the sample, added in ascending frame order in fp64 together with the window's
 //     squares, divided where that sum exceeds FLT_MIN.  No atomics: the same bits on every run.
 // sat_griffin_lim: init_kernel (angles = exp(i init_phase), prev = 0; the only sincos), then per
 //   iteration inverse_kernel (spectrum = mag * angles), overlap_add_kernel into the intermediate
-//   waveform and analysis_kernel: the pair-of-frames forward FFT of audio.hip on the reflect-padded
+//   waveform and analysis_kernel: the core's forward FFT of frame pairs of the reflect-padded
 //   intermediate waveform, whose separated spectra give t = reb - c prev, prev = reb and the new
 //   unit phasors t / (|t| + 1e-16) in fp64 around the fp32 butterflies.  A last inverse +
 //   overlap-add writes the caller's waveform.  Everything is queued on the caller's stream; nothing
@@ -27,7 +24,7 @@
 // the last synthesis needs the stand-alone kernel anyway.
 #include <cfloat>
 
-#include "sat_common.h"
+#include "stft.h"
 
 using namespace sat;
 
@@ -44,25 +41,6 @@ __device__ __forceinline__ int valid_frames(int F, int F_max, int hop, int half_
   if (F < 1 || F > F_max) return 0;
   const int64_t L = (int64_t)hop * (F - 1);
   return (L > half_n && L <= stride) ? F : 0;
-}
-
-template <bool kInverse>
-__device__ __forceinline__ void fft_passes(float2* z, const float2* tw, int log2n, int half_n,
-                                           int tid) {
-  for (int s = 0; s < log2n; ++s) {
-    const int half = 1 << s, tshift = log2n - 1 - s;
-    for (int j = tid; j < half_n; j += 256) {
-      const int pos = j & (half - 1);
-      const int i0 = ((j >> s) << (s + 1)) + pos, i1 = i0 + half;
-      float2 w = tw[pos << tshift];
-      if (kInverse) w.y = -w.y;
-      const float2 a = z[i0], c = z[i1];
-      const float tr = c.x * w.x - c.y * w.y, ti = c.x * w.y + c.y * w.x;
-      z[i0] = make_float2(a.x + tr, a.y + ti);
-      z[i1] = make_float2(a.x - tr, a.y - ti);
-    }
-    __syncthreads();
-  }
 }
 
 // ------------------------------------------------------------------ mel -> linear
@@ -206,13 +184,6 @@ __global__ void __launch_bounds__(256) init_kernel(GlP p, int64_t total) {
   if (p.prev) p.prev[i] = make_float2(0.f, 0.f);
 }
 
-__device__ __forceinline__ int reflect_index(int f, int j, int hop, int half_n, int L) {
-  int i = f * hop + j - half_n;
-  if (i < 0) i = -i;
-  if (i >= L) i = 2 * (L - 1) - i;
-  return i;
-}
-
 __device__ __forceinline__ void update_phase(const GlP& p, int64_t i, double re, double im) {
   double tr = re, ti = im;
   if (p.prev) {
@@ -236,28 +207,14 @@ __global__ void __launch_bounds__(256) analysis_kernel(GlP p) {
   const bool have1 = f1 < F;
   const int L = p.hop * (F - 1);                        // frames of it: 1 + L / hop = F again
   const float* y = p.x + (int64_t)b * p.x_stride;
-  const int shift = 32 - p.log2n;
-  for (int j = tid; j < n; j += 256) {
-    const float w = p.window[j];
-    float v0 = 0.f, v1 = 0.f;
-    if (w != 0.f) {
-      v0 = w * y[reflect_index(f0, j, p.hop, half_n, L)];
-      if (have1) v1 = w * y[reflect_index(f1, j, p.hop, half_n, L)];
-    }
-    z[__brev((unsigned)j) >> shift] = make_float2(v0, v1);
-  }
-  for (int j = tid; j < half_n; j += 256) tw[j] = p.twiddle[j];
-  __syncthreads();
-
+  stft_gather_pair(z, tw, y, L, f0, f1, have1, p.window, p.twiddle, n, p.log2n, p.hop, tid);
   fft_passes<false>(z, tw, p.log2n, half_n, tid);
 
   const int64_t row0 = ((int64_t)b * p.F_max + f0) * nf;
   for (int k = tid; k < nf; k += 256) {
-    const float2 a = z[k], c = z[(n - k) & (n - 1)];
-    const double r0 = 0.5 * ((double)a.x + c.x), i0 = 0.5 * ((double)a.y - c.y);
-    const double r1 = 0.5 * ((double)a.y + c.y), i1 = 0.5 * ((double)c.x - a.x);
-    update_phase(p, row0 + k, r0, i0);
-    if (have1) update_phase(p, row0 + nf + k, r1, i1);
+    const BinPair x = separate_bin(z, k, n);
+    update_phase(p, row0 + k, x.r0(), x.i0());
+    if (have1) update_phase(p, row0 + nf + k, x.r1(), x.i1());
   }
 }
 
@@ -270,14 +227,7 @@ struct Stft {
 // the checks the synthesis entries share; returns SAT_OK or the refusal's code
 int check_stft(const char* who, const Stft& s) {
   const int n = s.n_fft;
-  if (n < 64 || n > 4096 || (n & (n - 1)) != 0) {
-    set_error("%s: n_fft %d is not a power of two in 64..4096", who, n);
-    return SAT_ERR_UNSUPPORTED;
-  }
-  SAT_CHECK_ARG(s.win >= 1 && s.win <= n, "%s: win %d outside 1..n_fft %d", who, s.win, n);
-  SAT_CHECK_ARG(s.hop >= 1, "%s: hop %d < 1", who, s.hop);
-  SAT_CHECK_ARG(s.num_freq == n / 2 + 1, "%s: num_freq %d != n_fft/2 + 1 = %d", who, s.num_freq,
-                n / 2 + 1);
+  if (const int rc = check_stft_config(who, n, s.hop, s.win, s.num_freq)) return rc;
   SAT_CHECK_ARG(s.B >= 0 && s.B <= 65535 && s.F_max >= 0 && s.wav_stride >= 0, "%s: bad sizes",
                 who);
   SAT_CHECK_ARG(s.B == 0 || (s.frames && s.frames_host), "%s: null pointer (frames)", who);
@@ -293,17 +243,10 @@ int check_stft(const char* who, const Stft& s) {
   return SAT_OK;
 }
 
-int ilog2(int n) {
-  int l = 0;
-  while ((1 << l) < n) ++l;
-  return l;
-}
-
 // inverse FFT of every pair of frames into fb, then the gather into wav
 int launch_synthesis(const char* who, SynthP p, void* stream) {
-  const size_t lds = (size_t)12 * p.n_fft;
-  hipLaunchKernelGGL(inverse_kernel, dim3((p.F_max + 1) / 2, p.B), dim3(256), lds,
-                     as_stream(stream), p);
+  hipLaunchKernelGGL(inverse_kernel, dim3((p.F_max + 1) / 2, p.B), dim3(256),
+                     stft_lds_bytes(p.n_fft), as_stream(stream), p);
   SAT_LAUNCH_CHECK(who);
   hipLaunchKernelGGL(overlap_add_kernel, dim3((p.wav_stride + 255) / 256, p.B), dim3(256), 0,
                      as_stream(stream), p);
@@ -421,7 +364,7 @@ extern "C" int sat_griffin_lim(const SatGriffinLim* d, void* stream) {
   for (int it = 0; it < d->n_iter; ++it) {
     if (const int rc = launch_synthesis("sat_griffin_lim", p, stream)) return rc;
     hipLaunchKernelGGL(analysis_kernel, dim3((d->F_max + 1) / 2, d->B), dim3(256),
-                       (size_t)12 * n, as_stream(stream), g);
+                       stft_lds_bytes(n), as_stream(stream), g);
     SAT_LAUNCH_CHECK("sat_griffin_lim");
   }
   p.wav = d->wav;

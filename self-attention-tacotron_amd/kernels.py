@@ -1126,22 +1126,37 @@ def image_render(src, base, rows, cols, col_stride, minmax, canvas, rows_host=No
     _lib.call("sat_image_render", *args, _p(minmax), _p(canvas), _stream())
 
 
-# ---- audio front end (csrc/audio.hip; sat_amd/audio.py)
+# ---- audio front end and vocoder (csrc/audio.hip, trim.hip, resample.hip, vocoder.hip;
+#      sat_amd/audio.py).  Only dtypes and buffer sizes are checked here: what an entry refuses,
+#      it refuses itself.
+def _contiguous(what, dtype, **tensors):
+    for name, t in tensors.items():
+        if t is not None and (t.dtype != dtype or not t.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous "
+                             f"{str(dtype).replace('torch.', '')} tensor")
+
+
+def _lengths_i32(what, name, dev, host, B):
+    _contiguous(what, torch.int32, **{name: dev})
+    if dev.numel() != B or len(host) != B:
+        raise ValueError(f"{what}: {name} must be an int32 [B] tensor with its host copy")
+    return _host_i32(host, B)
+
+
+def _stft_tables(what, n_fft, window, twiddle):
+    if window.numel() < n_fft or twiddle.numel() < n_fft:
+        raise ValueError(f"{what}: window and twiddle table need n_fft floats each")
+
+
 def melspec(wav, lengths, lengths_host, *, n_fft, hop, win, window, twiddle, basis, band_lo,
             band_hi, ref_level_db, amp_floor, out, mag_out=None, offsets=None, offsets_host=None):
     """Batch of waveforms ``wav`` [B, stride] -> mel dB ``out`` [B, F_max, num_mels] (and the
     magnitudes ``mag_out`` [B, F_max, num_freq]) in one launch; see include/sat_abi.h.  With
     ``offsets`` (device int32 [B]) and its host copy, utterance b is the segment of ``lengths[b]``
-    samples that starts at ``wav[b, offsets[b]]``.  Only dtypes and buffer sizes are checked here:
-    what the entry refuses, it refuses itself."""
-    for name, t in (("wav", wav), ("window", window), ("twiddle", twiddle), ("basis", basis),
-                    ("out", out), ("mag_out", mag_out)):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise ValueError(f"melspec: {name} must be a contiguous float32 tensor")
-    for name, t in (("lengths", lengths), ("band_lo", band_lo), ("band_hi", band_hi),
-                    ("offsets", offsets)):
-        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
-            raise ValueError(f"melspec: {name} must be a contiguous int32 tensor")
+    samples that starts at ``wav[b, offsets[b]]``."""
+    _contiguous("melspec", torch.float32, wav=wav, window=window, twiddle=twiddle, basis=basis,
+                out=out, mag_out=mag_out)
+    _contiguous("melspec", torch.int32, band_lo=band_lo, band_hi=band_hi, offsets=offsets)
     if wav.dim() != 2 or basis.dim() != 2 or out.dim() != 3:
         raise ValueError("melspec: wav [B, stride], basis [num_mels, num_freq], out [B, F, num_mels]")
     B, stride = wav.shape
@@ -1150,15 +1165,13 @@ def melspec(wav, lengths, lengths_host, *, n_fft, hop, win, window, twiddle, bas
     if out.shape != (B, F_max, num_mels) or (mag_out is not None
                                              and mag_out.shape != (B, F_max, num_freq)):
         raise ValueError("melspec: out [B, F, num_mels] / mag_out [B, F, num_freq] expected")
-    if (lengths.numel() != B or len(lengths_host) != B or band_lo.numel() != num_mels
-            or band_hi.numel() != num_mels):
-        raise ValueError("melspec: lengths need B entries, band_lo / band_hi num_mels entries")
-    if window.numel() < n_fft or twiddle.numel() < n_fft:
-        raise ValueError("melspec: window and twiddle table need n_fft floats each")
+    if band_lo.numel() != num_mels or band_hi.numel() != num_mels:
+        raise ValueError("melspec: band_lo / band_hi need num_mels entries")
+    _stft_tables("melspec", n_fft, window, twiddle)
     if (offsets is not None and offsets.numel() != B) or (offsets_host is not None
                                                           and len(offsets_host) != B):
         raise ValueError("melspec: offsets need B entries")
-    keep, host = _host_i32(lengths_host, B)
+    keep, host = _lengths_i32("melspec", "lengths", lengths, lengths_host, B)
     keep_off, off_host = _host_i32(offsets_host, B)
     d = _lib.SatMelSpec(B=B, wav_stride=stride, n_fft=int(n_fft), hop=int(hop), win=int(win),
                         num_mels=num_mels, num_freq=num_freq, F_max=F_max,
@@ -1173,13 +1186,13 @@ def melspec(wav, lengths, lengths_host, *, n_fft, hop, win, window, twiddle, bas
 def mel_stats(mel, frames, out):
     """``out`` [B, 4, M] float64 = min, max, sum, sum of squares of ``mel`` [B, F_max, M] over each
     utterance's first ``frames`` [B] (int32) rows."""
-    if mel.dtype != torch.float32 or not mel.is_contiguous() or mel.dim() != 3:
-        raise ValueError("mel_stats: mel must be a contiguous float32 [B, F_max, M] tensor")
+    _contiguous("mel_stats", torch.float32, mel=mel)
+    _contiguous("mel_stats", torch.int32, frames=frames)
+    _contiguous("mel_stats", torch.float64, out=out)
+    if mel.dim() != 3 or frames.numel() != mel.shape[0] \
+            or out.shape != (mel.shape[0], 4, mel.shape[2]):
+        raise ValueError("mel_stats: mel [B, F_max, M], frames [B], out [B, 4, M]")
     B, F_max, M = mel.shape
-    if frames.dtype != torch.int32 or not frames.is_contiguous() or frames.numel() != B:
-        raise ValueError("mel_stats: frames must be a contiguous int32 [B] tensor")
-    if out.dtype != torch.float64 or not out.is_contiguous() or out.shape != (B, 4, M):
-        raise ValueError("mel_stats: out must be a contiguous float64 [B, 4, M] tensor")
     _lib.call("sat_mel_stats", _p(mel), _p(frames), B, F_max, M, _p(out), _stream())
 
 
@@ -1187,19 +1200,14 @@ def trim_bounds(wav, lengths, lengths_host, *, frame_length, hop, top_db, pad_sa
                 frame_ms):
     """Silence-trim bounds of a batch of waveforms ``wav`` [B, stride] in one entry call:
     ``bounds`` [B, 2] int32 = (start, stop) of each utterance, ``frame_ms`` [B, ms_stride] float32
-    the frame mean squares it is decided from; see include/sat_abi.h.  Only dtypes and buffer
-    sizes are checked here: what the entry refuses, it refuses itself."""
-    for name, t in (("wav", wav), ("frame_ms", frame_ms)):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
-            raise ValueError(f"trim_bounds: {name} must be a contiguous float32 [B, n] tensor")
-    for name, t in (("lengths", lengths), ("bounds", bounds)):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError(f"trim_bounds: {name} must be a contiguous int32 tensor")
+    the frame mean squares it is decided from; see include/sat_abi.h."""
+    _contiguous("trim_bounds", torch.float32, wav=wav, frame_ms=frame_ms)
+    _contiguous("trim_bounds", torch.int32, bounds=bounds)
+    if wav.dim() != 2 or frame_ms.dim() != 2 or bounds.shape != (wav.shape[0], 2) \
+            or frame_ms.shape[0] != wav.shape[0]:
+        raise ValueError("trim_bounds: wav [B, stride], bounds [B, 2], frame_ms [B, ms_stride]")
     B, stride = wav.shape
-    if (lengths.numel() != B or len(lengths_host) != B or bounds.shape != (B, 2)
-            or frame_ms.shape[0] != B):
-        raise ValueError("trim_bounds: lengths [B], bounds [B, 2], frame_ms [B, ms_stride]")
-    keep, host = _host_i32(lengths_host, B)
+    keep, host = _lengths_i32("trim_bounds", "lengths", lengths, lengths_host, B)
     _lib.call("sat_trim_bounds", _p(wav), _p(lengths), host, B, stride, int(frame_length),
               int(hop), float(top_db), int(pad_samples), _p(bounds), _p(frame_ms),
               frame_ms.shape[1], _stream())
@@ -1209,44 +1217,25 @@ def resample(wav, lengths, lengths_host, *, table, L, M, offset, scale, out):
     """Batch of waveforms ``wav`` [B, stride_in] at one rate -> ``out`` [B, stride_out] at
     ``L / M`` times that rate in one launch: ``table`` [L, taps] holds each phase's filter row,
     whose first tap lies ``offset`` samples from ``floor(n M / L)``; ``out`` is written whole
-    (zeros past ``ceil(lengths[b] L / M)``); see include/sat_abi.h.  Only dtypes and buffer sizes
-    are checked here: what the entry refuses, it refuses itself."""
-    for name, t in (("wav", wav), ("table", table), ("out", out)):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
-            raise ValueError(f"resample: {name} must be a contiguous float32 2-D tensor")
-    if lengths.dtype != torch.int32 or not lengths.is_contiguous():
-        raise ValueError("resample: lengths must be a contiguous int32 tensor")
+    (zeros past ``ceil(lengths[b] L / M)``); see include/sat_abi.h."""
+    _contiguous("resample", torch.float32, wav=wav, table=table, out=out)
+    if wav.dim() != 2 or table.dim() != 2 or out.dim() != 2 or out.shape[0] != wav.shape[0]:
+        raise ValueError("resample: wav [B, stride_in], table [L, taps], out [B, stride_out]")
     B, stride_in = wav.shape
-    if lengths.numel() != B or len(lengths_host) != B or out.shape[0] != B:
-        raise ValueError("resample: lengths [B] with its host copy, out [B, stride_out]")
     if table.shape[0] != int(L):
         raise ValueError(f"resample: table has {table.shape[0]} rows for {L} phases")
-    keep, host = _host_i32(lengths_host, B)
+    keep, host = _lengths_i32("resample", "lengths", lengths, lengths_host, B)
     _lib.call("sat_resample", _p(wav), _p(lengths), host, B, stride_in, _p(table), int(L), int(M),
               table.shape[1], int(offset), float(scale), _p(out), out.shape[1], _stream())
-
-
-# ---- vocoder (csrc/vocoder.hip; sat_amd/audio.py)
-def _contiguous_f32(what, **tensors):
-    for name, t in tensors.items():
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous float32 tensor")
-
-
-def _frames_i32(what, frames, frames_host, B):
-    if frames.dtype != torch.int32 or not frames.is_contiguous() or frames.numel() != B \
-            or len(frames_host) != B:
-        raise ValueError(f"{what}: frames must be a contiguous int32 [B] tensor with its host copy")
-    return _host_i32(frames_host, B)
 
 
 def mel_to_linear(mel, frames, frames_host, *, inv_basis, average, stddev, ref_level_db, power,
                   out):
     """Normalised ``mel`` [B, F_max, M] -> linear magnitudes ``out`` [B, F_max, num_freq]
     (``max(1e-10, inv_basis @ 10^(dB / 20)) ** power``), rows past ``frames`` zero; see
-    include/sat_abi.h.  Only dtypes and buffer sizes are checked here."""
-    _contiguous_f32("mel_to_linear", mel=mel, inv_basis=inv_basis, average=average,
-                    stddev=stddev, out=out)
+    include/sat_abi.h."""
+    _contiguous("mel_to_linear", torch.float32, mel=mel, inv_basis=inv_basis, average=average,
+                stddev=stddev, out=out)
     if mel.dim() != 3 or inv_basis.dim() != 2:
         raise ValueError("mel_to_linear: mel [B, F, M], inv_basis [num_freq, M]")
     B, F_max, M = mel.shape
@@ -1255,7 +1244,7 @@ def mel_to_linear(mel, frames, frames_host, *, inv_basis, average, stddev, ref_l
             or out.shape != (B, F_max, num_freq):
         raise ValueError("mel_to_linear: inv_basis [num_freq, M], average / stddev [M], "
                          "out [B, F, num_freq] expected")
-    keep, host = _frames_i32("mel_to_linear", frames, frames_host, B)
+    keep, host = _lengths_i32("mel_to_linear", "frames", frames, frames_host, B)
     _lib.call("sat_mel_to_linear", _p(mel), _p(frames), host, B, F_max, M, num_freq,
               _p(inv_basis), _p(average), _p(stddev), float(ref_level_db), float(power), _p(out),
               _stream())
@@ -1264,13 +1253,12 @@ def mel_to_linear(mel, frames, frames_host, *, inv_basis, average, stddev, ref_l
 def istft(spec, frames, frames_host, *, n_fft, hop, win, window, twiddle, wav):
     """Complex ``spec`` [B, F_max, num_freq, 2] (float32 re / im) -> ``wav`` [B, stride], utterance
     b in its first ``hop * (frames[b] - 1)`` samples and zeros after; see include/sat_abi.h."""
-    _contiguous_f32("istft", spec=spec, window=window, twiddle=twiddle, wav=wav)
+    _contiguous("istft", torch.float32, spec=spec, window=window, twiddle=twiddle, wav=wav)
     if spec.dim() != 4 or spec.shape[3] != 2 or wav.dim() != 2 or wav.shape[0] != spec.shape[0]:
         raise ValueError("istft: spec [B, F, num_freq, 2], wav [B, stride]")
     B, F_max, num_freq, _ = spec.shape
-    if window.numel() < n_fft or twiddle.numel() < n_fft:
-        raise ValueError("istft: window and twiddle table need n_fft floats each")
-    keep, host = _frames_i32("istft", frames, frames_host, B)
+    _stft_tables("istft", n_fft, window, twiddle)
+    keep, host = _lengths_i32("istft", "frames", frames, frames_host, B)
     lib = _lib.load()
     nbytes = int(lib.sat_istft_scratch_bytes(B, F_max, int(n_fft)))
     scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=spec.device)
@@ -1284,15 +1272,14 @@ def griffin_lim(mag, init_phase, frames, frames_host, *, n_fft, hop, win, window
     """Griffin-Lim on the magnitudes ``mag`` [B, F_max, num_freq] from the start phases
     ``init_phase`` (radians, same shape) into ``wav`` [B, stride]: the whole loop is queued on the
     current stream; see include/sat_abi.h."""
-    _contiguous_f32("griffin_lim", mag=mag, init_phase=init_phase, window=window,
-                    twiddle=twiddle, wav=wav)
+    _contiguous("griffin_lim", torch.float32, mag=mag, init_phase=init_phase, window=window,
+                twiddle=twiddle, wav=wav)
     if mag.dim() != 3 or init_phase.shape != mag.shape or wav.dim() != 2 \
             or wav.shape[0] != mag.shape[0]:
         raise ValueError("griffin_lim: mag and init_phase [B, F, num_freq], wav [B, stride]")
     B, F_max, num_freq = mag.shape
-    if window.numel() < n_fft or twiddle.numel() < n_fft:
-        raise ValueError("griffin_lim: window and twiddle table need n_fft floats each")
-    keep, host = _frames_i32("griffin_lim", frames, frames_host, B)
+    _stft_tables("griffin_lim", n_fft, window, twiddle)
+    keep, host = _lengths_i32("griffin_lim", "frames", frames, frames_host, B)
     lib = _lib.load()
     nbytes = int(lib.sat_griffin_lim_scratch_bytes(B, F_max, int(n_fft), int(hop),
                                                    1 if momentum > 0 else 0))
