@@ -49,7 +49,8 @@ extern "C" {
  * and SatGriffinLim): purely additive -- new symbols and one new struct, no existing struct or
  * signature touched -- so a binding of 13 without them reads a library with them correctly.
  * Still 13 with the L2 regulariser (sat_l2_regularize, sat_workspace_l2): two new symbols.
- * Still 13 with the resampler (sat_resample): one new symbol. */
+ * Still 13 with the resampler (sat_resample): one new symbol.
+ * Still 13 with the VQ-code kernels (sat_codes_batch, sat_codes_argmax): two new symbols. */
 #define SAT_ABI_VERSION 13
 
 /* ---------------------------------------------------------------- library */
@@ -1195,6 +1196,44 @@ int sat_istft(const float* spec, const int32_t* frames, const int32_t* frames_ho
 int64_t sat_griffin_lim_scratch_bytes(int32_t B, int32_t F_max, int32_t n_fft, int32_t hop,
                                       int32_t momentum_on);
 int sat_griffin_lim(const SatGriffinLim* d, void* stream);
+
+/* ---------------------------------------------------------------- VQ-code batches
+ * The fork's targets are one-hot code frames (datasets/codes/dataset.py): a frame is one integer
+ * in 0..C-1.  A batch travels as indices and is expanded on the device.
+ *   sat_codes_batch: idx [n_idx] int32 holds the utterances' code indices one after another,
+ *     offsets [B + 1] int64 their bounds (offsets[0] = 0, offsets[B] = n_idx), T_b = offsets[b + 1]
+ *     - offsets[b].  ONE launch writes every element of every output exactly once (nothing is
+ *     cleared first):
+ *       codes [B][T_pad][C]          one-hot of idx inside each utterance, all-zero rows from T_b on
+ *                                    (the reference's padded_batch value 0, dataset.py:302-362);
+ *       done [B][T_pad / r]          1 at step T_b / r - 1, 0 elsewhere;
+ *       code_loss_mask, binary_loss_mask [B][T_pad]   1 for t < T_b, 0 from there on;
+ *       target_length [B] int64      T_b.
+ *     Rows are stored 16 bytes at a time where C % 4 == 0 (codes then 16-byte aligned), one float
+ *     at a time for any other C >= 1.  An index outside 0..C-1 is never used as an address: its
+ *     row is written as zeros and *err (device, 8-byte aligned, 0 before the call) becomes
+ *     ~((b << 32) | t) of the LOWEST such (utterance b, position t), by a 64-bit atomic max, so
+ *     the word does not depend on the order of the waves; it stays as it was when every index is
+ *     in range.  offsets (device) is what the kernel reads, offsets_host the caller's HOST copy,
+ *     which the entry checks; a device length the entry would have refused is clamped to
+ *     0..T_pad and reads nothing past idx + n_idx.  Two runs give identical bits.
+ *     Refused before anything is launched (SAT_ERR_ARGUMENT): B < 0, C < 1, r < 1, T_pad < 1,
+ *     T_pad % r != 0, a null pointer (B > 0), offsets_host[0] != 0, any T_b < 1, T_pad < max T_b,
+ *     offsets_host[B] != n_idx, codes not 16-byte (C % 4 == 0) or 4-byte aligned, idx / done / a
+ *     mask not 4-byte aligned, offsets / target_length / err not 8-byte aligned.
+ *   sat_codes_argmax: x [R] rows of C floats, ldx floats apart -> out [R] int32, the index of each
+ *     row's maximum; a tie goes to the lowest index and a NaN ranks above every number (the first
+ *     NaN wins), as numpy.argmax.  With onehot != NULL also onehot[row][c] = (c == out[row]) for
+ *     c < C, rows ld_onehot floats apart.  One wave per row above 32 columns, 64 / G rows per wave
+ *     for the smallest power of two G >= C below; a fixed reduction order, no atomics: two runs
+ *     give identical bits.  Refused (SAT_ERR_ARGUMENT): R < 0, C < 1, ldx < C, ld_onehot < C with
+ *     onehot, a null x / out (R > 0), a pointer that is not 4-byte aligned. */
+int sat_codes_batch(const int32_t* idx, int64_t n_idx, const int64_t* offsets,
+                    const int64_t* offsets_host, int32_t B, int32_t C, int32_t T_pad, int32_t r,
+                    float* codes, float* done, float* code_loss_mask, float* binary_loss_mask,
+                    int64_t* target_length, uint64_t* err, void* stream);
+int sat_codes_argmax(const float* x, int64_t ldx, int32_t R, int32_t C, int32_t* out,
+                     float* onehot, int64_t ld_onehot, void* stream);
 
 /* ---------------------------------------------------------------- dataset records (host)
  * TFRecord framing of the dataset path: datasets/ljspeech/dataset.py:96-112 reads

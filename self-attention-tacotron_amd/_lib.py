@@ -293,6 +293,8 @@ SIGNATURES.update({
     "sat_mel_to_linear": [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _F, _P, _P],
     "sat_istft": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _I64, _P],
     "sat_griffin_lim": [ctypes.POINTER(SatGriffinLim), _P],
+    "sat_codes_batch": [_P, _I64, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
+    "sat_codes_argmax": [_P, _I64, _I32, _I32, _P, _P, _I64, _P],
 })
 
 RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),

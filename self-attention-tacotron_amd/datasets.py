@@ -30,6 +30,16 @@ gives ``VCTKSourceDataForPrediction`` (:49-61).  The reference's padding values 
 speaker fields (0, 0, -1, :299-301) pad scalars, which a padded batch never does: a short last
 batch simply has fewer rows.
 
+Codes (``datasets/codes/dataset.py``, the fork's default): ``CodesDatasetSource`` reads the VCTK
+source record with the phone fields required (:66-97) and a target record of code frames, dense
+one-hot as the reference writes it or as int32 indices (``tfrecord.parse_preprocessed_code_data``
+reduces a dense record to indices).  ``outputs_per_step`` must be 1: the reference sets
+``target_length = codes_length * r`` over ``codes_length`` rows (:188), no silence frames, no
+rounding.  A batch stays indices (``CodeBatch``: the concatenated indices and their offsets);
+``model_fn`` uploads those and ``sat_codes_batch`` writes ``codes`` (padding value 0, :351),
+``done``, the two masks and ``target_length`` on the device.  ``done`` is padded with 0 there, not
+the reference's 1 (:354): those steps carry ``binary_loss_mask`` 0, so no loss term reads them.
+
 Randomness (``shuffle``) uses ``numpy.random.default_rng(seed)`` -- the same buffer algorithm as
 tf.data's shuffle (fill ``buffer_size``, emit a uniformly chosen slot, refill it), not its
 random stream.
@@ -72,6 +82,28 @@ class VCTKSourceDataForPrediction(namedtuple("VCTKSourceDataForPrediction",
                                              ["id", "key", "source", "source_length",
                                               "speaker_id", "age", "gender", "text", "mel",
                                               "mel_width", "target_length"])):
+    pass
+
+
+class CodeData(namedtuple("CodeData", ["id", "key", "code_index", "codes_length", "codes_width",
+                                      "target_length"])):
+    """One code target as indices (datasets/codes/dataset.py:45-48 holds the dense ``codes``,
+    ``done`` and the two masks, which here are made on the device for the whole batch)."""
+
+
+class CodeBatch(namedtuple("CodeBatch", ["id", "key", "code_index", "offsets", "codes_width",
+                                         "codes_length", "target_length"])):
+    """A batch of code targets before expansion: ``code_index`` int32 holds the utterances' codes
+    one after another, ``offsets`` int64 [B + 1] their bounds.  ``model_fn`` uploads these two and
+    has ``sat_codes_batch`` write ``codes`` [B, max target_length, codes_width], ``done`` and the
+    loss masks."""
+
+
+class CodesSourceDataForPrediction(namedtuple("CodesSourceDataForPrediction",
+                                              ["id", "key", "source", "source_length",
+                                               "speaker_id", "age", "gender", "text",
+                                               "code_index", "offsets", "codes_width",
+                                               "codes_length", "target_length"])):
     pass
 
 
@@ -221,6 +253,27 @@ def prepare_vctk_source(s: R.PreprocessedVCTKSourceData, hparams) -> VCTKSourceD
                           s.text)
 
 
+def prepare_code_target(t: R.PreprocessedCodeData, hparams) -> CodeData:
+    """datasets/codes/dataset.py:159-232 at r = 1: no silence frames, ``target_length =
+    codes_length``."""
+    if int(t.codes_width) != int(hparams.num_mels):
+        raise ValueError(f"code record {t.key!r}: codes_width {t.codes_width} != "
+                         f"hparams.num_mels {hparams.num_mels}")
+    if int(t.codes_length) < 1:
+        raise ValueError(f"code record {t.key!r}: no codes")
+    return CodeData(t.id, t.key, t.code_index, np.int64(t.codes_length), int(t.codes_width),
+                    np.int64(t.codes_length))
+
+
+def prepare_codes_source(s: R.PreprocessedVCTKSourceData, hparams) -> VCTKSourceData:
+    """datasets/codes/dataset.py:145-155: as the VCTK source; records written without a phone
+    front end hold empty phone fields, which ``source == 'phone'`` cannot use."""
+    if hparams.source == 'phone' and not int(s.phone_length or 0):
+        raise ValueError(f"hparams.source is 'phone' but record {s.key!r} has no phones (records "
+                         "written without a phone front end need source='char')")
+    return prepare_vctk_source(s, hparams)
+
+
 def _pad_stack(arrays, pad_value, dtype):
     n = max(a.shape[0] for a in arrays)
     out = np.full((len(arrays), n) + arrays[0].shape[1:], pad_value, dtype)
@@ -245,6 +298,16 @@ def padded_batch(elems, hparams):
                            gender=np.array([x.gender for x in src], np.int64), **cols)
     else:
         s = SourceData(**cols)
+    if isinstance(tgt[0], CodeData):
+        lengths = np.array([x.codes_length for x in tgt], np.int64)
+        offsets = np.zeros(len(tgt) + 1, np.int64)
+        np.cumsum(lengths, out=offsets[1:])
+        return s, CodeBatch(id=np.array([x.id for x in tgt], np.int64),
+                            key=np.array([x.key for x in tgt], object),
+                            code_index=np.concatenate([x.code_index for x in tgt]).astype(np.int32),
+                            offsets=offsets, codes_width=int(tgt[0].codes_width),
+                            codes_length=lengths,
+                            target_length=np.array([x.target_length for x in tgt], np.int64))
     t = MelData(id=np.array([x.id for x in tgt], np.int64),
                 key=np.array([x.key for x in tgt], object),
                 mel=_pad_stack([x.mel for x in tgt], sil, np.float32),
@@ -316,6 +379,38 @@ class VCTKDatasetSource(DatasetSource):
             for s, t in zip(src, tgt):
                 yield (prepare_vctk_source(R.parse_preprocessed_vctk_source_data(s), hp),
                        prepare_target(R.parse_preprocessed_mel_data(t), hp))
+        return ZippedDataset(_Dataset(gen), hp)
+
+
+class CodesDatasetSource(DatasetSource):
+    """datasets/codes/dataset.py:101-242: the code corpus.  Source records are the VCTK ones with
+    the phone fields required; target records hold code frames, dense one-hot or as indices
+    (``tfrecord.parse_preprocessed_code_data``), and stay indices up to the device."""
+
+    def __init__(self, source, target, hparams):
+        if int(hparams.outputs_per_step) != 1:
+            # dataset.py:188 sets target_length = codes_length * r over codes_length rows, which
+            # is consistent only at r = 1 (its default)
+            # (worded as the factory words every combination it has no dataset for)
+            raise ValueError(f"Unknown dataset: {hparams.dataset} with outputs_per_step="
+                             f"{hparams.outputs_per_step} (the codes dataset exists for "
+                             "outputs_per_step=1 only)")
+        super().__init__(source, target, hparams)
+
+    @staticmethod
+    def create_from_tfrecord_files(source_files, target_files, hparams, cycle_length=4,
+                                   buffer_output_elements=None, prefetch_input_elements=None):
+        return CodesDatasetSource(interleave_files(list(source_files), cycle_length),
+                                  interleave_files(list(target_files), cycle_length), hparams)
+
+    def prepare_and_zip(self) -> "ZippedDataset":
+        hp = self.hparams
+        src, tgt = self.source, self.target
+
+        def gen():
+            for s, t in zip(src, tgt):
+                yield (prepare_codes_source(R.parse_preprocessed_codes_source_data(s), hp),
+                       prepare_code_target(R.parse_preprocessed_code_data(t), hp))
         return ZippedDataset(_Dataset(gen), hp)
 
 
@@ -417,6 +512,9 @@ class BatchedDataset(DatasetBase):
     def merge_target_to_source(self):
         """:306-320."""
         def convert(s, t: MelData):
+            if isinstance(t, CodeBatch):
+                return CodesSourceDataForPrediction(*s, t.code_index, t.offsets, t.codes_width,
+                                                    t.codes_length, t.target_length), t
             if isinstance(s, VCTKSourceData):
                 return VCTKSourceDataForPrediction(*s, t.mel, t.mel_width, t.target_length), t
             return SourceDataForPrediction(s.id, s.key, s.source, s.source_length, s.text,
@@ -426,23 +524,27 @@ class BatchedDataset(DatasetBase):
 
 _LJSPEECH_NAMES = ("ljspeech.dataset.DatasetSource", "datasets.ljspeech.dataset.DatasetSource")
 _VCTK_NAMES = ("vctk.dataset.DatasetSource", "datasets.vctk.dataset.DatasetSource")
+_CODES_NAMES = ("codes.dataset.DatasetSource", "datasets.codes.dataset.DatasetSource")
 
 
 def dataset_factory(source, target, hparams):
     """datasets/dataset_factory.py:15-23 with the LJSpeech entry enabled (it is commented out
-    in the fork, :12) and the VCTK one; other names raise ValueError as the reference's factory
-    would."""
+    in the fork, :12), the VCTK one and the fork's own codes one; other names raise ValueError as
+    the reference's factory would."""
     if hparams.dataset in _LJSPEECH_NAMES:
         return DatasetSource(source, target, hparams)
     if hparams.dataset in _VCTK_NAMES:
         return VCTKDatasetSource(source, target, hparams)
+    if hparams.dataset in _CODES_NAMES:
+        return CodesDatasetSource(source, target, hparams)
     raise ValueError(f"Unknown dataset: {hparams.dataset}")
 
 
 def create_from_tfrecord_files(source_files, target_files, hparams, cycle_length=4,
                                buffer_output_elements=None, prefetch_input_elements=None):
     """datasets/dataset_factory.py:26-32 (LJSpeech entry enabled)."""
-    for names, cls in ((_LJSPEECH_NAMES, DatasetSource), (_VCTK_NAMES, VCTKDatasetSource)):
+    for names, cls in ((_LJSPEECH_NAMES, DatasetSource), (_VCTK_NAMES, VCTKDatasetSource),
+                       (_CODES_NAMES, CodesDatasetSource)):
         if hparams.dataset in names:
             return cls.create_from_tfrecord_files(source_files, target_files, hparams,
                                                   cycle_length, buffer_output_elements,
@@ -468,3 +570,11 @@ class vctk:
     DatasetSource = VCTKDatasetSource
     SourceData = VCTKSourceData
     SourceDataForPrediction = VCTKSourceDataForPrediction
+
+
+class codes:
+    """The reference's names for the code classes (``datasets.codes.dataset``)."""
+    DatasetSource = CodesDatasetSource
+    SourceData = VCTKSourceData
+    CodeData = CodeData
+    SourceDataForPrediction = CodesSourceDataForPrediction

@@ -287,6 +287,26 @@ VCTK_SELF_ATTENTION_OVERRIDES = dict(
 )
 
 
+# examples/codes/self-attention-tacotron.json: the fork's own corpus of VQ-code targets.
+CODES_SELF_ATTENTION_OVERRIDES = {
+    "initial_learning_rate": 0.002, "outputs_per_step": 1, "max_iters": 450,
+    "attention": "forward", "cumulative_weights": False, "attention_kernel": 10,
+    "attention_filters": 5, "use_zoneout_at_encoder": False, "decoder_version": "v2",
+    "dataset": "codes.dataset.DatasetSource", "target_file_extension": "target.tfrecord",
+    "save_checkpoints_steps": 50, "tacotron_model": "DualSourceSelfAttentionTacotronModel",
+    "encoder": "SelfAttentionCBHGEncoder", "decoder": "DualSourceTransformerDecoder",
+    "use_speaker_embedding": False, "num_speakers": 152, "speaker_embedding_offset": 225,
+}
+
+
+def codes_hparams(num_codes: int, **extra: Any) -> HParams:
+    """The codes corpus with ``num_codes`` code values: a target frame is a one-hot of that
+    width, so ``num_mels = num_codes``; one frame per decoder step, one frame fed back."""
+    hp = HParams(**default_values()).override_from_dict(CODES_SELF_ATTENTION_OVERRIDES)
+    hp.override_from_dict({"num_mels": int(num_codes), "outputs_per_step": 1, "n_feed_frame": 1})
+    return hp.override_from_dict(extra) if extra else hp
+
+
 def ljspeech_hparams(**extra: Any) -> HParams:
     hp = HParams(**default_values()).override_from_dict(LJSPEECH_SELF_ATTENTION_OVERRIDES)
     return hp.override_from_dict(extra) if extra else hp

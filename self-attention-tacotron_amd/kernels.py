@@ -1291,3 +1291,101 @@ def griffin_lim(mag, init_phase, frames, frames_host, *, n_fft, hop, win, window
                            twiddle=_p(twiddle), wav=_p(wav), scratch=_p(scratch),
                            scratch_bytes=nbytes)
     _lib.check(lib.sat_griffin_lim(ctypes.byref(d), _stream()), "sat_griffin_lim")
+
+
+# ---- VQ-code batches (csrc/codes.hip; sat_amd/datasets.py, sat_amd/predict_code.py)
+_CODES_ERR = {}
+
+
+def codes_error_word(device) -> torch.Tensor:
+    """The device error word of ``codes_batch`` (int64 [1], zero while no index was refused), one
+    per device, made on first use; ``codes_batch`` clears it again after reporting."""
+    device = torch.device(device)
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    w = _CODES_ERR.get(key)
+    if w is None:
+        w = torch.zeros(1, dtype=torch.int64, device=device)
+        _CODES_ERR[key] = w
+    return w
+
+
+def codes_batch(idx, offsets, offsets_host, *, C, T_pad, r=1, codes=None, done=None,
+                code_loss_mask=None, binary_loss_mask=None, target_length=None, err=None,
+                check=True):
+    """One launch from the code indices ``idx`` (int32, the utterances one after another) and
+    their bounds ``offsets`` (int64 [B + 1], with the host copy ``offsets_host``) to the padded
+    training batch: ``codes`` [B, T_pad, C] one-hot, ``done`` [B, T_pad / r], the two loss masks
+    [B, T_pad] and ``target_length`` [B] int64; see include/sat_abi.h.  Outputs that are not given
+    are allocated (uninitialised: the kernel writes every element).  With ``check`` the error word
+    is read back (a synchronisation) and an index outside 0..C-1 raises ``ValueError`` naming the
+    utterance and the position; without it the caller reads ``err`` when it chooses to."""
+    _contiguous("codes_batch", torch.int32, idx=idx)
+    _contiguous("codes_batch", torch.int64, offsets=offsets, target_length=target_length, err=err)
+    _contiguous("codes_batch", torch.float32, codes=codes, done=done,
+                code_loss_mask=code_loss_mask, binary_loss_mask=binary_loss_mask)
+    B = offsets.numel() - 1
+    if offsets.dim() != 1 or B < 0 or len(offsets_host) != B + 1:
+        raise ValueError("codes_batch: offsets must be an int64 [B + 1] tensor with its host copy")
+    C, T_pad, r = int(C), int(T_pad), int(r)
+    dev = idx.device
+    steps = T_pad // r if r >= 1 else 0
+    shapes = {"codes": (B, T_pad, C), "done": (B, steps), "code_loss_mask": (B, T_pad),
+              "binary_loss_mask": (B, T_pad), "target_length": (B,)}
+    out = {"codes": codes, "done": done, "code_loss_mask": code_loss_mask,
+           "binary_loss_mask": binary_loss_mask, "target_length": target_length}
+    for name, shape in shapes.items():
+        if out[name] is None:
+            out[name] = torch.empty([max(int(s), 0) for s in shape], device=dev,
+                                    dtype=torch.int64 if name == "target_length"
+                                    else torch.float32)
+        elif tuple(out[name].shape) != shape:
+            raise ValueError(f"codes_batch: {name} is {tuple(out[name].shape)}, expected {shape}")
+    if err is None:
+        err = codes_error_word(dev)
+    if err.numel() != 1:
+        raise ValueError("codes_batch: err must be an int64 [1] tensor")
+    host = (ctypes.c_int64 * (B + 1))(*[int(v) for v in offsets_host])
+    _lib.call("sat_codes_batch", _p(idx), idx.numel(), _p(offsets),
+              ctypes.cast(host, ctypes.c_void_p), B, C, T_pad, r, _p(out["codes"]),
+              _p(out["done"]), _p(out["code_loss_mask"]), _p(out["binary_loss_mask"]),
+              _p(out["target_length"]), _p(err), _stream())
+    out["err"] = err
+    if check:
+        word = int(err.item())
+        if word != 0:
+            err.zero_()
+            key = ~word & 0xFFFFFFFFFFFFFFFF
+            b, t = key >> 32, key & 0xFFFFFFFF
+            value = int(idx[int(offsets_host[b]) + t].item())
+            raise ValueError(f"codes_batch: utterance {b}, position {t}: code index {value} is "
+                             f"outside 0..{C - 1}")
+    return out
+
+
+def codes_argmax(x, out=None, onehot=None):
+    """``x`` [..., C] float32 (rows a fixed stride apart, the last axis contiguous) -> int32
+    indices of each row's maximum, ties to the lowest index; ``onehot`` (float32, the shape of
+    ``x``, or True to allocate it) also receives the one-hot rows; see include/sat_abi.h.
+    Returns ``out``, or ``(out, onehot)`` with a one-hot."""
+    if x.dtype != torch.float32 or x.dim() < 1 or x.stride(-1) != 1:
+        raise ValueError("codes_argmax: x must be float32 with a contiguous last axis")
+    C = x.shape[-1]
+    x2 = x if x.dim() == 2 else x.reshape(-1, C) if x.is_contiguous() else None
+    if x2 is None:
+        raise ValueError("codes_argmax: x must be [R, C] with a row stride, or contiguous")
+    R = x2.shape[0]
+    ldx = x2.stride(0) if R > 1 else max(C, x2.stride(0))
+    if out is None:
+        out = torch.empty(x.shape[:-1], dtype=torch.int32, device=x.device)
+    _contiguous("codes_argmax", torch.int32, out=out)
+    if out.numel() != R:
+        raise ValueError(f"codes_argmax: out has {out.numel()} entries for {R} rows")
+    if onehot is True:
+        onehot = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if onehot is not None:
+        _contiguous("codes_argmax", torch.float32, onehot=onehot)
+        if onehot.numel() != R * C:
+            raise ValueError("codes_argmax: onehot must have the shape of x")
+    _lib.call("sat_codes_argmax", _p(x2), int(ldx), R, C, _p(out), _p(onehot) or None, C,
+              _stream())
+    return out if onehot is None else (out, onehot)

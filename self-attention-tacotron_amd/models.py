@@ -349,7 +349,47 @@ class DualSourceSelfAttentionTacotronModel:
         step = float(global_step * step_factor + 1)
         return init_rate * warmup ** 0.5 * min(step * warmup ** -1.5, step ** -0.5)
 
+    def _code_batch(self, features, labels):
+        """A batch of code targets that is still indices (datasets.CodeBatch): the indices and
+        their offsets are uploaded through the stager and ONE launch (sat_codes_batch) writes the
+        one-hot ``mel``, ``done``, the two masks and ``target_length`` on the device.  The indices
+        are range-checked here on the host, so the kernel's error word is not read back (that
+        would make the host wait for the stream every step)."""
+        from . import kernels as K
+        dev = self.engine.device
+        C, r = int(self.params.num_mels), int(self.params.outputs_per_step)
+        if r != 1:      # binary_loss_mask is per frame there (datasets/codes/dataset.py:219)
+            raise ValueError(f"code batches need outputs_per_step=1, got {r}")
+        if int(labels.codes_width) != C:
+            raise ValueError(f"code batch of width {labels.codes_width}, hparams.num_mels is {C}")
+        idx = np.ascontiguousarray(labels.code_index, dtype=np.int32)
+        offsets = np.ascontiguousarray(labels.offsets, dtype=np.int64)
+        bad = np.flatnonzero((idx < 0) | (idx >= C))
+        if bad.size:
+            b = int(np.searchsorted(offsets, bad[0], side="right")) - 1
+            raise ValueError(f"code batch: utterance {b}, position {int(bad[0] - offsets[b])}: "
+                             f"code index {int(idx[bad[0]])} is outside 0..{C - 1}")
+        arrays = {"source": features.source, "source_length": features.source_length,
+                  "code_index": idx, "offsets": offsets}
+        dtypes = {"source": torch.int64, "source_length": torch.int64,
+                  "code_index": torch.int32, "offsets": torch.int64}
+        if self.params.use_speaker_embedding:                 # models/models.py:64-70
+            if getattr(features, "speaker_id", None) is not None:
+                arrays["speaker_id"], dtypes["speaker_id"] = features.speaker_id, torch.int64
+            elif self.engine.d.spk_fixed < 0:
+                raise ValueError("use_speaker_embedding=True needs features.speaker_id")
+        up = self._stager.upload(arrays, dev, dtypes)
+        lengths = np.diff(offsets)
+        T_pad = -(-int(lengths.max()) // r) * r
+        out = K.codes_batch(up.pop("code_index"), up.pop("offsets"), offsets, C=C, T_pad=T_pad,
+                            r=r, check=False)
+        up.update(mel=out["codes"], mel_mask=out["code_loss_mask"], done=out["done"],
+                  done_mask=out["binary_loss_mask"], target_length=out["target_length"])
+        return up
+
     def _batch(self, features, labels):
+        if hasattr(labels, "code_index"):
+            return self._code_batch(features, labels)
         dev = self.engine.device
         codes = labels.codes if hasattr(labels, "codes") else labels.mel
         cmask = (labels.code_loss_mask if hasattr(labels, "code_loss_mask")

@@ -29,6 +29,16 @@ whose trimmed length is <= n_fft/2 cannot be framed: it is skipped with a warnin
 ``list.csv``.  Both corpora share the batching, the writer thread, the statistics and the two
 output files.
 
+``Codes(in_dir, out_dir, hparams, num_codes, version)`` reads the VQ-code corpus of
+preprocess/codes.py: the speaker table as VCTK's, per speaker the files ``p<id>*.txt`` of
+``in_dir``, each holding ``text<TAB>codes`` on its first line.  ``version`` 0 keeps all codes, 1 or
+2 every second one starting at ``version - 1``.  The source record has the VCTK fields plus the
+phone fields (empty: there is no flite here, so ``hparams.phoneme`` must be ``none``) and ``lang``;
+the target record holds the one-hot frames dense, as the reference, or as int32 indices
+(``--compact``).  A first line without a tab is skipped with a warning and left out of
+``list.csv``.  CLI: ``python -m sat_amd.preprocess codes <in_dir> <out_dir> --num-codes C
+[--version V] [--speaker-info F] [--compact]`` plus the shared options below (no ``--resample``).
+
 CLI: ``python -m sat_amd.preprocess {ljspeech | vctk} <in_dir> <out_dir> [--hparam-json-file F]
 [--hparams S] [--source-only | --target-only] [--resample]``; ``vctk`` also takes
 ``--version 0.8``.
@@ -396,6 +406,108 @@ class VCTK(_Corpus):
         return kept, mel, frames
 
 
+class TxtCodeRecord(namedtuple("TxtCodeRecord",
+                               ["id", "key", "txt_path", "code_path", "speaker_info"])):
+    pass
+
+
+class Codes:
+    """preprocess/codes.py:90-176 + preprocess_vqcodes.py: a folder of ``p<id>_*.txt`` files whose
+    first line is ``text<TAB>codes`` (codes separated by blanks) becomes source and target
+    records.  No audio and no device work: a target is ``num_codes``-wide one-hot frames, written
+    dense as the reference does or, with ``compact``, as int32 indices."""
+
+    def __init__(self, in_dir, out_dir, hparams, num_codes, version=0,
+                 speaker_info_filename=None, cleaner: Callable[[str], str] = basic_cleaners,
+                 compact: bool = False):
+        if hparams.phoneme != "none":
+            raise ValueError(f"phoneme={hparams.phoneme!r}: phone labels need flite, which is not "
+                             "built here; preprocess with phoneme=none (the records then hold "
+                             "empty phone fields and train with source='char')")
+        if int(version) not in (0, 1, 2):
+            raise ValueError(f"codes version {version}: 0 (all codes), 1 or 2 (every second one)")
+        if int(num_codes) < 1:
+            raise ValueError(f"num_codes {num_codes} < 1")
+        self.in_dir, self.out_dir, self.hparams = in_dir, out_dir, hparams
+        self.num_codes, self.version = int(num_codes), int(version)
+        self.speaker_info_filename = (speaker_info_filename if speaker_info_filename is not None
+                                      else os.path.join(in_dir, "speaker-info.txt"))
+        self.cleaner, self.compact = cleaner, bool(compact)
+        self.skipped: List[str] = []
+
+    def _load_speaker_info(self):
+        with open(self.speaker_info_filename, mode='r', encoding='utf8') as f:
+            for line in f.readlines()[1:]:
+                si = line.split()
+                if not si or si[0] == "315":
+                    continue
+                yield SpeakerInfo(int(si[0]), int(si[1]), 0 if si[2] == 'F' else 1)
+
+    def list_files(self) -> List[TxtCodeRecord]:
+        """:100-124.  The key is the file name without its extension (``os.path.splitext``); the
+        reference's ``strip('.txt')`` also eats trailing ``t`` and ``x`` characters of the key."""
+        names = sorted(os.listdir(self.in_dir))
+        out: List[TxtCodeRecord] = []
+        for si in self._load_speaker_info():
+            for name in names:
+                if name.endswith('.txt') and name.startswith(f"p{si.id}"):
+                    path = os.path.join(self.in_dir, name)
+                    out.append(TxtCodeRecord(len(out), os.path.splitext(name)[0], path, path, si))
+        return out
+
+    def read_record(self, r: TxtCodeRecord):
+        """``(text, code indices)`` of a file's first line (:140-151, :165-167); None for a line
+        that is not ``text<TAB>codes``."""
+        with open(r.code_path, mode='r', encoding='utf8') as f:
+            parts = f.readline().rstrip("\n").split("\t")
+        if len(parts) != 2:
+            return None
+        codes = [int(c) for c in parts[1].split(" ") if c != ""]
+        if self.version >= 1:
+            codes = codes[self.version - 1::2]
+        return parts[0], np.array(codes, dtype=np.int32)
+
+    def source_path(self, key):
+        return os.path.join(self.out_dir, f"{key}.source.tfrecord")
+
+    def target_path(self, key):
+        return os.path.join(self.out_dir, f"{key}.target.tfrecord")
+
+    def _skip(self, r, why):
+        print(f"warning: skipping {r.key}: {why}", file=sys.stderr)
+        self.skipped.append(r.key)
+
+    def run(self, process_source: bool = True, process_target: bool = True) -> List[str]:
+        os.makedirs(self.out_dir, exist_ok=True)
+        keys = []
+        for r in self.list_files():
+            rec = self.read_record(r)
+            if rec is None:
+                self._skip(r, "the first line is not text<TAB>codes")
+                continue
+            text, codes = rec
+            if codes.size == 0:
+                self._skip(r, "no codes")
+                continue
+            if codes.min() < 0 or codes.max() >= self.num_codes:
+                raise ValueError(f"{r.code_path}: a code outside 0..{self.num_codes - 1}")
+            if process_source:
+                sequence, clean_text = text_to_sequence(text, self.cleaner)
+                si = r.speaker_info
+                tfrecord.write_preprocessed_codes_source_data(
+                    r.id, r.key, np.array(sequence, dtype=np.int64), clean_text, si.id, si.age,
+                    si.gender, self.source_path(r.key))
+            if process_target:
+                tfrecord.write_preprocessed_code_data(r.id, r.key, codes, self.num_codes,
+                                                      self.target_path(r.key), self.compact)
+            keys.append(r.key)
+        with open(os.path.join(self.out_dir, 'list.csv'), 'w', newline='') as csvfile:
+            w = csv.writer(csvfile)
+            for key in keys:
+                w.writerow([key])
+        return keys
+
+
 def main(argv=None) -> int:
     from .hparams import create_hparams, hparams_debug_string
     ap = argparse.ArgumentParser(prog="python -m sat_amd.preprocess",
@@ -404,7 +516,16 @@ def main(argv=None) -> int:
     lj = sub.add_parser("ljspeech", help="LJSpeech-1.1 layout: metadata.csv and wavs/")
     vc = sub.add_parser("vctk", help="VCTK-Corpus 0.8 layout: speaker-info.txt, wav48/, txt/")
     vc.add_argument("--version", default="0.8", help="corpus version (only 0.8)")
-    for p in (lj, vc):
+    cd = sub.add_parser("codes", help="VQ-code corpus: speaker-info.txt and p<id>_*.txt files "
+                                      "holding text<TAB>codes")
+    cd.add_argument("--num-codes", type=int, required=True, help="code values (one-hot width)")
+    cd.add_argument("--version", type=int, default=0,
+                    help="0: all codes; 1 or 2: every second code from the first / second")
+    cd.add_argument("--speaker-info", default=None,
+                    help="speaker table (default <in_dir>/speaker-info.txt)")
+    cd.add_argument("--compact", action="store_true",
+                    help="targets as int32 code indices instead of dense one-hot rows")
+    for p in (lj, vc, cd):
         p.add_argument("in_dir")
         p.add_argument("out_dir")
         p.add_argument("--hparam-json-file", default=None, help="JSON file of hyper-parameters")
@@ -412,13 +533,17 @@ def main(argv=None) -> int:
         only = p.add_mutually_exclusive_group()
         only.add_argument("--source-only", action="store_true")
         only.add_argument("--target-only", action="store_true")
+    for p in (lj, vc):
         p.add_argument("--resample", action="store_true",
                        help="bring wavs at another rate to hparams.sample_rate on the GPU "
                             "(default: such a file is an error)")
     args = ap.parse_args(argv)
     hp = create_hparams(args.hparam_json_file, args.hparams)
     print(hparams_debug_string(hp))
-    if args.dataset == "vctk":
+    if args.dataset == "codes":
+        corpus = Codes(args.in_dir, args.out_dir, hp, args.num_codes, version=args.version,
+                       speaker_info_filename=args.speaker_info, compact=args.compact)
+    elif args.dataset == "vctk":
         corpus = VCTK(args.in_dir, args.out_dir, hp, version=args.version,
                       resample=args.resample)
     else:

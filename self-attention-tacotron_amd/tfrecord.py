@@ -17,7 +17,11 @@ Restates what the reference's data path reads and writes:
 * the VCTK source record of preprocess/vctk.py:31-44, which adds ``speaker_id, age, gender``, and
   its parser (datasets/vctk/dataset.py:64-96), which also takes the ``phone, phone_length,
   phone_txt`` fields of the phone front end when a record carries them (None otherwise).  VCTK
-  target records are the LJSpeech ones.
+  target records are the LJSpeech ones;
+* the VQ-code records of preprocess/codes.py:20-49: the source record with the phone fields and
+  ``lang``, the target record ``id, key, lang, codes (float32 one-hot bytes), codes_length,
+  codes_width`` -- or, compact, ``code_index`` (int32 bytes) in place of ``codes`` -- parsed to
+  indices either way, and the prediction record of utils/tfrecord.py:144-157.
 """
 
 from __future__ import annotations
@@ -46,6 +50,20 @@ class PreprocessedVCTKSourceData(namedtuple("PreprocessedVCTKSourceData",
 
 class PreprocessedMelData(namedtuple("PreprocessedMelData",
                                      ["id", "key", "mel", "target_length", "mel_width"])):
+    pass
+
+
+class PreprocessedCodeData(namedtuple("PreprocessedCodeData",
+                                      ["id", "key", "lang", "code_index", "codes_length",
+                                       "codes_width"])):
+    """A code target as indices: ``code_index`` int32 [codes_length], each in 0..codes_width-1
+    (utils/tfrecord.py:21-23 holds the dense ``codes`` instead)."""
+
+
+class CodePredictionResult(namedtuple("CodePredictionResult",
+                                      ["id", "key", "codes", "codes_length", "codes_width",
+                                       "ground_truth_codes", "ground_truth_codes_length", "text",
+                                       "source", "source_length"])):
     pass
 
 
@@ -302,3 +320,148 @@ def parse_preprocessed_vctk_source_data(record: bytes) -> PreprocessedVCTKSource
         speaker_id=_scalar(ex, "speaker_id", "int64"), age=_scalar(ex, "age", "int64"),
         gender=_scalar(ex, "gender", "int64"), text=_scalar(ex, "text", "bytes"),
         phone=phone, phone_length=phone_length, phone_txt=phone_txt)
+
+
+# ---------------------------------------------------------------- VQ-code records
+def codes_source_example(_id: int, key: str, source: np.ndarray, text: str, speaker_id: int,
+                         age: int, gender: int, phone: np.ndarray = None, phone_txt: str = "",
+                         lang: str = "EN") -> bytes:
+    """preprocess/codes.py:33-49: the VCTK source fields, the three phone fields (always present;
+    empty without a phone front end) and ``lang``."""
+    phone = np.zeros(0, np.int64) if phone is None else phone
+    ex = decode_example(vctk_source_example(_id, key, source, text, speaker_id, age, gender,
+                                            phone, phone_txt))
+    ex["lang"] = ("bytes", [lang.encode("utf-8")])
+    return encode_example(ex)
+
+
+def write_preprocessed_codes_source_data(_id, key, source, text, speaker_id, age, gender,
+                                         filename, phone=None, phone_txt="", lang="EN") -> None:
+    write_tfrecords([codes_source_example(_id, key, source, text, speaker_id, age, gender, phone,
+                                          phone_txt, lang)], filename)
+
+
+def parse_preprocessed_codes_source_data(record: bytes) -> PreprocessedVCTKSourceData:
+    """datasets/codes/dataset.py:66-97: every field is required, the phone fields included."""
+    ex = decode_example(record)
+    for name, kind in (("phone", "bytes"), ("phone_length", "int64"), ("phone_txt", "bytes")):
+        _scalar(ex, name, kind)
+    return parse_preprocessed_vctk_source_data(record)
+
+
+def one_hot_to_index(codes: np.ndarray, key="") -> np.ndarray:
+    """int32 indices of dense one-hot rows [T, C]; a row that is not exactly one 1.0 among zeros
+    is a ``ValueError`` naming ``key`` and the row."""
+    codes = np.asarray(codes)
+    if codes.ndim != 2 or codes.shape[1] < 1:
+        raise ValueError(f"code record {key!r}: codes must be [codes_length, codes_width]")
+    ok = ((codes == 1).sum(axis=1) == 1) & ((codes != 0).sum(axis=1) == 1)
+    if not ok.all():
+        raise ValueError(f"code record {key!r}: row {int(np.argmin(ok))} is not one-hot")
+    return codes.argmax(axis=1).astype(np.int32)
+
+
+def index_to_one_hot(index: np.ndarray, width: int) -> np.ndarray:
+    """float32 [len(index), width] one-hot rows (preprocess/codes.py:154-157)."""
+    index = np.asarray(index, np.int64)
+    if index.size and (index.min() < 0 or index.max() >= width):
+        bad = int(np.argmax((index < 0) | (index >= width)))
+        raise ValueError(f"code {int(index[bad])} at position {bad} is outside 0..{width - 1}")
+    out = np.zeros((index.size, int(width)), np.float32)
+    out[np.arange(index.size), index] = 1.0
+    return out
+
+
+def code_target_example(_id: int, key: str, code_index: np.ndarray, codes_width: int,
+                        compact: bool = False, lang: str = "EN") -> bytes:
+    """The code target record.  Dense (preprocess/codes.py:20-30): ``codes`` = raw float32
+    [codes_length, codes_width] one-hot bytes; compact: ``code_index`` = raw int32 [codes_length]
+    instead.  Both carry ``id, key, lang, codes_length, codes_width``."""
+    code_index = np.ascontiguousarray(code_index, dtype="<i4")
+    dense = index_to_one_hot(code_index, codes_width)        # also the range check
+    feats = {"id": ("int64", [_id]), "key": ("bytes", [key.encode("utf-8")]),
+             "lang": ("bytes", [lang.encode("utf-8")])}
+    if compact:
+        feats["code_index"] = ("bytes", [code_index.tobytes()])
+    else:
+        feats["codes"] = ("bytes", [dense.astype("<f4").tobytes()])
+    feats["codes_length"] = ("int64", [len(code_index)])
+    feats["codes_width"] = ("int64", [int(codes_width)])
+    return encode_example(feats)
+
+
+def write_preprocessed_code_data(_id: int, key: str, code_index: np.ndarray, codes_width: int,
+                                 filename: str, compact: bool = False, lang: str = "EN") -> None:
+    write_tfrecords([code_target_example(_id, key, code_index, codes_width, compact, lang)],
+                    filename)
+
+
+def parse_preprocessed_code_data(record: bytes) -> PreprocessedCodeData:
+    """parse_preprocessed_code_data + decode_preprocessed_code_data (utils/tfrecord.py:89-113) for
+    both layouts; a dense record is reduced to indices here, on the host."""
+    ex = decode_example(record)
+    key = _scalar(ex, "key", "bytes")
+    name = key.decode("utf-8", errors="replace")
+    length = _scalar(ex, "codes_length", "int64")
+    width = _scalar(ex, "codes_width", "int64")
+    if width < 1 or length < 0:
+        raise ValueError(f"code record {name!r}: codes_length {length}, codes_width {width}")
+    if "code_index" in ex:
+        index = np.frombuffer(_scalar(ex, "code_index", "bytes"), "<i4").astype(np.int32)
+        if index.size != length:
+            raise ValueError(f"code record {name!r}: {index.size} indices, codes_length {length}")
+        if index.size and (index.min() < 0 or index.max() >= width):
+            bad = int(np.argmax((index < 0) | (index >= width)))
+            raise ValueError(f"code record {name!r}: code {int(index[bad])} at position {bad} is "
+                             f"outside 0..{width - 1}")
+    else:
+        dense = np.frombuffer(_scalar(ex, "codes", "bytes"), "<f4")
+        if dense.size != length * width:
+            raise ValueError(f"code record {name!r}: {dense.size} floats do not fill "
+                             f"[{length}, {width}]")
+        index = one_hot_to_index(dense.reshape(length, width), name)
+    lang = ex["lang"][1][0] if "lang" in ex and ex["lang"][1] else b""
+    return PreprocessedCodeData(id=_scalar(ex, "id", "int64"), key=key, lang=lang,
+                                code_index=index, codes_length=length, codes_width=width)
+
+
+def prediction_result_example(_id: int, key: str, codes: np.ndarray,
+                              ground_truth_codes: np.ndarray, text: str,
+                              source: np.ndarray) -> bytes:
+    """utils/tfrecord.py:144-157 (write_prediction_result's Example; its ``alignments`` and
+    ``accent_type`` arguments are not written there either)."""
+    codes = np.ascontiguousarray(codes, dtype="<f4")
+    truth = np.ascontiguousarray(ground_truth_codes, dtype="<f4")
+    source = np.ascontiguousarray(source, dtype="<i8")
+    return encode_example({
+        "id": ("int64", [_id]), "key": ("bytes", [key.encode("utf-8")]),
+        "codes": ("bytes", [codes.tobytes()]),
+        "codes_length": ("int64", [codes.shape[0]]),
+        "codes_width": ("int64", [codes.shape[1]]),
+        "ground_truth_codes": ("bytes", [truth.tobytes()]),
+        "ground_truth_codes_length": ("int64", [truth.shape[0]]),
+        "text": ("bytes", [text.encode("utf-8")]),
+        "source": ("bytes", [source.tobytes()]),
+        "source_length": ("int64", [source.shape[0]])})
+
+
+def write_prediction_result(_id, key, codes, ground_truth_codes, text, source, filename) -> None:
+    write_tfrecords([prediction_result_example(_id, key, codes, ground_truth_codes, text,
+                                               source)], filename)
+
+
+def parse_prediction_result(record: bytes) -> CodePredictionResult:
+    """postprocess_vqcodes.py:15-49, with the code rows read as the float32 they were written
+    as (the script reads them as int32 words, which has the same argmax)."""
+    ex = decode_example(record)
+    n, w = _scalar(ex, "codes_length", "int64"), _scalar(ex, "codes_width", "int64")
+    gn = _scalar(ex, "ground_truth_codes_length", "int64")
+    return CodePredictionResult(
+        id=_scalar(ex, "id", "int64"), key=_scalar(ex, "key", "bytes"),
+        codes=np.frombuffer(_scalar(ex, "codes", "bytes"), "<f4").reshape(n, w),
+        codes_length=n, codes_width=w,
+        ground_truth_codes=np.frombuffer(_scalar(ex, "ground_truth_codes", "bytes"),
+                                         "<f4").reshape(gn, w),
+        ground_truth_codes_length=gn, text=_scalar(ex, "text", "bytes"),
+        source=np.frombuffer(_scalar(ex, "source", "bytes"), "<i8").astype(np.int64),
+        source_length=_scalar(ex, "source_length", "int64"))
