@@ -374,6 +374,15 @@ typedef struct SatDecodePersistent {
 } SatDecodePersistent;
 int64_t sat_decode_persistent_scratch_bytes(void);
 int sat_decode_persistent(const SatDecodePersistent* a, void* stream);
+/* The same decode with the decoder prenets' dropout kept on (apply_dropout_on_inference; the
+ * reference hands the switch to its PreNets, modules/module.py:1511-1517): after the ReLU, prenet
+ * layer l's output (t, b, col) is multiplied by the value sat_rng_fill(seed_ptr, stream_l, keep,
+ * 1 / keep) writes at element (t*B + b)*P_l + col of a step-major [T][B][P_l] tensor (P_0 = 256,
+ * P_1 = 128).  The words are drawn inside the kernel, one Philox call per produced element; no
+ * mask touches memory.  seed_ptr[0] is read by the launch and left unchanged (the caller advances
+ * it, sat_counter_add).  A separate kernel instantiation: sat_decode_persistent is unaffected. */
+int sat_decode_persistent_dropout(const SatDecodePersistent* a, const uint64_t* seed_ptr,
+                                  uint64_t stream0, uint64_t stream1, float keep, void* stream);
 
 /* ---------------------------------------------------------------- (Zoneout)LSTM step
  * One time step of TF LSTMCell wrapped in ext tacotron2 ZoneoutLSTMCell,

@@ -241,6 +241,8 @@ SIGNATURES = {
     "sat_decode_attention_step": [_P, _I64, _I64, _I32, _I32, _I32, _I32, _F, _P, _I32, _P,
                                   _I64, _P],
     "sat_decode_persistent": [ctypes.POINTER(SatDecodePersistent), _P],
+    "sat_decode_persistent_dropout": [ctypes.POINTER(SatDecodePersistent), _P, _U64, _U64, _F,
+                                      _P],
     "sat_zlstm_step_fwd": [ctypes.POINTER(SatLstmFwd), _P],
     "sat_zlstm_step_bwd": [ctypes.POINTER(SatLstmBwd), _P],
     "sat_attn_param_grad_rows": [_I32, _I32],

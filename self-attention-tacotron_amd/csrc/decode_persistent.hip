@@ -37,6 +37,7 @@
 // every utterance) reads the B stop granules at the end of step t: every workgroup of every group
 // sees the same values and leaves the loop at the same step.
 #include "persistent.h"
+#include "philox.h"
 
 #include <algorithm>
 
@@ -148,7 +149,21 @@ __device__ __forceinline__ void gather(__amdgpu_buffer_rsrc_t r, int base4, int 
   }
 }
 
-__global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersistent p) {
+// What the in-kernel mask draw of the kDrop = true instantiation needs (prenet dropout at
+// inference, apply_dropout_on_inference).  kDrop = false carries an empty struct and no trace
+// of the draw: the two are separate kernels.
+template <bool kDrop>
+struct DropArgs {};
+template <>
+struct DropArgs<true> {
+  const uint64_t* seed;      // device word, read once (the host advances it after the launch)
+  uint64_t stream0, stream1; // Philox stream ids of the [T][B][256] / [T][B][128] masks
+  float keep, on;            // keep probability, value of a surviving element (1 / keep)
+};
+
+template <bool kDrop>
+__global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersistent p,
+                                                                DropArgs<kDrop> args) {
   const int g = blockIdx.x % kG, w = blockIdx.x / kG;
   if (g >= p.B) return;   // no utterance: no partner outside this group
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -282,6 +297,11 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
   float4 att_early = make_float4(0.f, 0.f, 0.f, 0.f);   // recurrent part of the next attention RNN step
   float4 l2_early = make_float4(0.f, 0.f, 0.f, 0.f);    // recurrent part of the next LSTM2 step
   const float scale = p.scale;
+  uint2 dkey = make_uint2(0u, 0u);   // kDrop: the Philox key = the seed's two halves
+  if constexpr (kDrop) {
+    const uint64_t sd = args.seed[0];
+    dkey = make_uint2((uint32_t)sd, (uint32_t)(sd >> 32));
+  }
 
 #if SAT_DP_TRACE
   __shared__ long long tacc[28], tabs[28];   // thread 0's segment clocks (LDS: no registers)
@@ -310,6 +330,13 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
     const int s = t & 1, sp = s ^ 1;
     const unsigned bt = lsb_tag(t), bp = lsb_tag(t - 1);
     // ================================================= P1: mel|stop of t-1, prenet layer 1 of t
+    // kDrop: this wave's word of the first prenet mask, the value sat_rng_fill writes at element
+    // (t B + g) 256 + cpre of the step-major [T][B][256] tensor -- formed before the gather, so
+    // it runs while z_{t-1} is still in flight (arithmetic only: no barrier, no memory access)
+    float dm0 = 1.f;
+    if constexpr (kDrop)
+      dm0 = rng_mask_value(((uint64_t)t * p.B + g) * kP0 + cpre, args.stream0, dkey, args.keep,
+                           args.on);
     if (t > 0) {
       gather<1>(R, (oZ + sp * kSD) / 4, kSD / 4, reinterpret_cast<float4*>(xz), bp, p.err);
       lds_barrier();
@@ -339,10 +366,17 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
         a = cbp0[wave];   // the go frame (zeros)
       }
       a = fmaxf(a, 0.f);
+      if constexpr (kDrop) a *= dm0;   // dropout after the ReLU (PreNet)
       if (lane == 0) stcx(xl, R, oY0 + s * kP0 + cpre, tagf(a, bt));
     }
     TP(3)
     // ================================================= P2: prenet layer 2
+    float dm1 = 1.f;   // kDrop: element (t B + g) 128 + cp1 of the [T][B][128] mask, as above
+    if constexpr (kDrop) {
+      if (wave < 4)
+        dm1 = rng_mask_value(((uint64_t)t * p.B + g) * kP1 + cp1, args.stream1, dkey, args.keep,
+                             args.on);
+    }
     gather<1>(R, (oY0 + s * kP0) / 4, kP0 / 4, reinterpret_cast<float4*>(xy0), bt, p.err);
     lds_barrier();
     TP(4)
@@ -351,6 +385,7 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
 #pragma unroll
       for (int i = 0; i < 4; ++i) a = fmaf(xy0[lane + 64 * i], wp1[i], a);
       a = fmaxf(wave_sum_dpp(a) + cbp1[wave], 0.f);
+      if constexpr (kDrop) a *= dm1;
       if (lane == 0) stcx(xl, R, oP + s * kP1 + cp1, tagf(a, bt));
     }
     TP(5)
@@ -724,7 +759,10 @@ extern "C" int64_t sat_decode_persistent_scratch_bytes(void) {
   return (kZeroDwords + kCacheFloats) * 4;
 }
 
-extern "C" int sat_decode_persistent(const SatDecodePersistent* a, void* stream) {
+// Argument checks, co-residency test, scratch clear and launch shared by the two entries.
+template <bool kDrop>
+static int launch_decode(const SatDecodePersistent* a, const DropArgs<kDrop>& args,
+                         void* stream) {
   SAT_CHECK_ARG(a && a->B >= 1 && a->B <= kG && a->N >= 1 && a->N <= kNM && a->T >= 1 &&
                     a->T <= kW * kRM,
                 "sat_decode_persistent: B <= 8, N <= 256, T <= 512 (got B=%d N=%d T=%d)",
@@ -743,7 +781,8 @@ extern "C" int sat_decode_persistent(const SatDecodePersistent* a, void* stream)
   int dev = 0, cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_persistent_kernel, kTh, 0) !=
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_persistent_kernel<kDrop>, kTh,
+                                                   0) !=
           hipSuccess) {
     set_error("sat_decode_persistent: device query failed");
     return SAT_ERR_HIP;
@@ -757,7 +796,26 @@ extern "C" int sat_decode_persistent(const SatDecodePersistent* a, void* stream)
     set_error("sat_decode_persistent: scratch clear failed");
     return SAT_ERR_HIP;
   }
-  hipLaunchKernelGGL(decode_persistent_kernel, dim3(kG * kW), dim3(kTh), 0, s, *a);
+  hipLaunchKernelGGL(decode_persistent_kernel<kDrop>, dim3(kG * kW), dim3(kTh), 0, s, *a, args);
   SAT_LAUNCH_CHECK("sat_decode_persistent");
   return SAT_OK;
+}
+
+extern "C" int sat_decode_persistent(const SatDecodePersistent* a, void* stream) {
+  return launch_decode<false>(a, DropArgs<false>{}, stream);
+}
+
+extern "C" int sat_decode_persistent_dropout(const SatDecodePersistent* a, const uint64_t* seed_ptr,
+                                             uint64_t stream0, uint64_t stream1, float keep,
+                                             void* stream) {
+  SAT_CHECK_ARG(a && seed_ptr, "sat_decode_persistent_dropout: null pointer");
+  SAT_CHECK_ARG(keep > 0.f, "sat_decode_persistent_dropout: keep must be > 0 (got %g)",
+                (double)keep);
+  DropArgs<true> args;
+  args.seed = seed_ptr;
+  args.stream0 = stream0;
+  args.stream1 = stream1;
+  args.keep = keep;
+  args.on = (float)(1.0 / (double)keep);
+  return launch_decode<true>(a, args, stream);
 }

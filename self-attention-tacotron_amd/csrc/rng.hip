@@ -1,6 +1,6 @@
 // Library plumbing (version, errors) and the counter-based mask generator.
 #include <cstdarg>
-#include "sat_common.h"
+#include "philox.h"
 
 namespace sat {
 
@@ -15,26 +15,7 @@ void set_error(const char* fmt, ...) {
 
 namespace {
 
-// Philox-4x32-10 (Salmon et al., SC'11): 4 x 32-bit outputs per (counter, key).
-__device__ __forceinline__ uint4 philox(uint4 ctr, uint2 key) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, ctr.x), lo0 = M0 * ctr.x;
-    const uint32_t hi1 = __umulhi(M1, ctr.z), lo1 = M1 * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += W0;
-    key.y += W1;
-  }
-  return ctr;
-}
-
-// u = (float)v * 2^-32 < keep.  (float)v rounds the 129 largest words up to 2^32, so u can be
-// exactly 1.0: keep >= 1 (a rate-0 mask) keeps every element outright instead of dropping those.
-// No draw with keep < 1 is affected.
-__device__ __forceinline__ bool rng_keep(uint32_t v, float keep) {
-  return keep >= 1.f || (float)v * 2.3283064365386963e-10f /* 2^-32 */ < keep;
-}
+// philox() and rng_keep(): philox.h
 
 __global__ void rng_fill_kernel(float* __restrict__ out, int64_t n, const uint64_t* seed_ptr,
                                 uint64_t stream_id, float keep, float on) {

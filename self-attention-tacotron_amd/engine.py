@@ -19,6 +19,13 @@ from .model import BNState, model_forward
 from .pipeline import Pipeline
 
 
+class EvalMasks(dict):
+    """Masks of a forward with ``training=False``: a name that is absent means "no mask"."""
+
+    def __missing__(self, name):
+        return None
+
+
 class Tacotron:
     def __init__(self, hp, device, seed: int = 1234,
                  init_values: Optional[Dict[str, np.ndarray]] = None, attn_tile: int = 32,
@@ -73,6 +80,10 @@ class Tacotron:
                 need_grad: bool = True):
         B, N = batch["source"].shape
         scratch = self.scratch(B, N) if self.persistent_decoder else None
+        if not training and masks is not None:
+            # apply_dropout_on_inference: the teacher-forced eval passes carry the decoder
+            # prenet masks alone; every other mask lookup answers None (eval semantics)
+            masks = EvalMasks(masks)
         return model_forward(self.P, self.bn, self.hp, self.d, batch, masks, training, self.ws,
                              compute_grad_seeds=need_grad, attn_tile=self.attn_tile,
                              pipe=self.pipe, persistent=self.persistent_decoder,

@@ -7,8 +7,8 @@ tacotron2 ``StopTokenBasedInferenceHelper`` (analog modules/helpers.py:111-160):
 
 * step 0 feeds the go frame (zeros), step t+1 the last predicted frame of step t
   (``mel_t[:, -num_mels * n_feed:]``);
-* the decoder cell is the training one in eval mode (no prenet dropout --
-  ``apply_dropout_on_inference=False``, hparams.py:105 -- zoneout blend);
+* the decoder cell is the training one in eval mode (zoneout blend; no prenet dropout unless
+  ``apply_dropout_on_inference`` is set, hparams.py:105 -- see "Prenet dropout" below);
 * ``TransformerWrapper`` re-runs the causal self-attention over the whole state history every
   step and keeps the last row.  Causal attention makes row t independent of later rows, so the
   row equals one query against a key/value cache of the history (the equivalence
@@ -41,11 +41,25 @@ Schedule: every buffer of a decode lives in a per-shape plan (static addresses),
 ``check_every`` steps can be captured once as a hipGraph (``graphs=True``) and replayed: the host
 issues one graph launch per chunk instead of ~30 kernel launches per step.
 
+Prenet dropout (``apply_dropout_on_inference=True``; the reference hands the switch to the
+decoder's PreNets, modules/module.py:1511-1517): the decoder prenets keep their dropout at rate
+``decoder_prenet_drop_rate`` while everything else keeps eval semantics.  The mask of prenet
+layer l is the ``sat_rng_fill`` draw of a step-major ``[T'][B][P_l]`` tensor (element
+``(t*B + b)*P_l + col``) on Philox stream ``DROP_STREAM0 + l`` from a seed word in device memory;
+the MultiSpeakerPreNet (layer 0 under ``speaker_embedd_to_prenet``) drops under ``is_training``
+only and so stays clean.  The launch path fills the masks of the whole decode in one
+``sat_rng_fill_segments`` launch before the loop (outside any captured graph) and multiplies row
+t in as the prenet products' ``mul`` epilogue; the one-launch decode draws the same words inside
+the kernel (``sat_decode_persistent_dropout``).  Every ``run()`` advances the seed by one on the
+device (``sat_counter_add``); the seed is not part of a checkpoint.
+
 Every arithmetic op is a libsat_hip kernel; torch allocates, views and copies.
 """
 
 from __future__ import annotations
 
+import ctypes
+import functools
 import math
 import warnings
 from typing import Dict, Optional
@@ -57,14 +71,60 @@ from . import kernels as K
 from .model import BNState, encoder_fwd, speaker_vector
 from .params import Dims
 
+# Philox stream id of the inference-time mask of decoder prenet layer l = DROP_STREAM0 + l
+# (fixed; the training step's mask arena uses ids 1..len(mask_specs), train.Trainer.reshape)
+DROP_STREAM0 = 1001
+
+
+def drop_on_value(keep: float) -> float:
+    """The value of a surviving element, 1 / keep, as sat_decode_persistent_dropout forms it:
+    the double quotient of the float32 ``keep``, rounded to float32 at the call."""
+    return 1.0 / ctypes.c_float(keep).value
+
+
+def prenet_drops(d: Dims):
+    """Which decoder prenet layers drop outside training under apply_dropout_on_inference:
+    every PreNet, but not the MultiSpeakerPreNet in front (multi_speaker_modules.py:31 drops
+    under is_training only)."""
+    return [not (d.multi_speaker and i == 0) for i in range(len(d.dec_prenet))]
+
+
+def prenet_mask_segments(d: Dims, Tm: int, B: int, keep: float):
+    """(arena floats, [(layer, offset, shape)], sat_rng_fill_segments tuples) of the step-major
+    prenet masks [T'][B][P_l] of one decode or teacher-forced pass; every mask starts on a
+    256-byte boundary (the GEMM epilogue's operand alignment)."""
+    off, views, segs = 0, [], []
+    on = drop_on_value(keep)
+    for i, drops in enumerate(prenet_drops(d)):
+        if not drops:
+            continue
+        n = Tm * B * d.dec_prenet[i]
+        views.append((i, off, (Tm, B, d.dec_prenet[i])))
+        segs.append((off, n, DROP_STREAM0 + i, keep, on))
+        off += (n + 63) // 64 * 64
+    return off, views, segs
+
+
+def draw_prenet_masks(d: Dims, Tm: int, B: int, keep: float, seed_dev: torch.Tensor):
+    """The masks of ``prenet_mask_segments`` drawn in ONE launch from ``seed_dev``, as the dict
+    the teacher-forced forward takes (``dec/prenet{l}``; a clean layer has no entry)."""
+    n, views, segs = prenet_mask_segments(d, Tm, B, keep)
+    arena = torch.empty(max(n, 1), device=seed_dev.device)
+    K.rng_fill_segments(arena, K.rng_segments(segs), seed_dev)
+    return {f"dec/prenet{i}": arena[off:off + math.prod(sh)].view(sh) for i, off, sh in views}
+
+
+def advance_seed(seed_dev: torch.Tensor) -> None:
+    _lib.call("sat_counter_add", seed_dev.data_ptr(), 1, K._stream())
+
 
 class _Plan:
     """Static buffers of one decode shape (B, N, T_max) plus the per-step launch closures."""
 
 
 class FreeRunningDecoder:
-    """Incremental decoding of a batch with eval semantics (no dropout, zoneout blend, BN moving
-    statistics).
+    """Incremental decoding of a batch with eval semantics (zoneout blend, BN moving statistics,
+    no dropout -- except the decoder prenets' under ``apply_dropout_on_inference``).
 
     ``helper``: ``"stop_token"`` (PREDICT, StopTokenBasedInferenceHelper: up to ``max_iters``
     steps, stops once every utterance's stop token fired after ``min_iters``) or
@@ -78,20 +138,41 @@ class FreeRunningDecoder:
     ``persistent``: run the whole decode as ONE launch (``sat_decode_persistent``) -- None picks
     it whenever the shape allows (mel feedback, no forced alignments, single speaker, the
     LJSpeech decoder dimensions, B <= 8, N <= 256, T' <= 512), True requires it, False keeps the
-    per-step launches."""
+    per-step launches.
+    ``seed``: the seed of the prenet masks under ``apply_dropout_on_inference`` -- an int (a
+    device word of its own is made) or a one-element int64 device tensor the caller shares
+    between decoders; every ``run()`` advances it by one.  Unused with the switch off.  With the
+    switch on the model must be on a GPU (the masks are device draws): the constructor raises
+    ``NotImplementedError`` otherwise."""
 
     def __init__(self, model, max_iters: Optional[int] = None, min_iters: int = 10,
                  check_every: int = 25, forced_alignments=None, feed: str = "mel",
                  helper: Optional[str] = None, graphs: bool = False,
-                 persistent: Optional[bool] = None):
+                 persistent: Optional[bool] = None, seed=1234):
         self.m = model
         self.hp = model.hp
         self.d: Dims = model.d
-        if getattr(self.hp, "apply_dropout_on_inference", False):
-            # PreNet(apply_dropout_on_inference=True) keeps prenet dropout at inference
-            # (modules/module.py:1513-1517); this build decodes with eval semantics only
-            raise NotImplementedError("apply_dropout_on_inference=True is not supported: "
-                                      "decoding runs with eval semantics (no prenet dropout)")
+        # PreNet(apply_dropout_on_inference=True) keeps prenet dropout at inference
+        # (modules/module.py:1511-1517)
+        self.drop = bool(getattr(self.hp, "apply_dropout_on_inference", False))
+        self.keep = 1.0 - float(self.hp.decoder_prenet_drop_rate)
+        self.seed = None
+        if self.drop:
+            # the masks are drawn by the device generator from a seed word in device memory:
+            # a model that is not on a GPU cannot honour the switch, and ignoring it silently
+            # would decode with other semantics than asked for
+            dev = getattr(model, "device", None)
+            if dev is None or torch.device(dev).type != "cuda":
+                raise NotImplementedError(
+                    "apply_dropout_on_inference=True is not supported for a model that is not "
+                    "on a GPU: the prenet masks are drawn on the device (sat_rng_fill)")
+            if isinstance(seed, torch.Tensor):
+                if seed.dtype != torch.int64 or seed.numel() != 1 or \
+                        seed.device.type != torch.device(model.device).type:
+                    raise ValueError("seed tensor must be one int64 word on the model's device")
+                self.seed = seed
+            else:
+                self.seed = torch.tensor([int(seed)], dtype=torch.int64, device=model.device)
         self.max_iters = int(self.hp.max_iters if max_iters is None else max_iters)
         self.min_iters = int(min_iters)
         self.check_every = max(1, int(check_every))
@@ -211,7 +292,11 @@ class FreeRunningDecoder:
         a1, a2 = "decoder/attention1", "decoder/attention2"
         self._pack_persistent(pl)
         pk = pl.pk
-        K.decode_persistent(
+        launch = K.decode_persistent
+        if self.drop:       # single speaker (_why_not): both prenet layers drop
+            launch = functools.partial(K.decode_persistent_dropout, self.seed, DROP_STREAM0,
+                                       DROP_STREAM0 + 1, self.keep)
+        launch(
             B=pl.B, N=pl.N, T=Tm, min_iters=self.min_iters,
             stop_mode=1 if self.helper == "stop_token" else 0,
             zc=hp.zoneout_factor_cell, zh=hp.zoneout_factor_output, u=0.5,
@@ -340,6 +425,17 @@ class FreeRunningDecoder:
         pl.SA_P = SA_P = [torch.zeros(B, H, Tm, Tm, **f32) for _ in range(d.dec_hops)]
         pl.state = state = torch.full((1,), -1, dtype=torch.int32, device=dev)
         pl.zero_each_run = [REC0X, C0, L1[0], L1[1], L2[0], L2[1], S1, AL1, S2, MS]
+        # apply_dropout_on_inference: the prenet masks of the whole decode, [T'][B][P_l] per
+        # dropping layer, filled by ONE launch per run before the loop (never inside a graph)
+        DM = [None] * len(d.dec_prenet)
+        pl.drop_arena = pl.drop_segs = None
+        if self.drop:
+            n, views, segs = prenet_mask_segments(d, Tm, B, self.keep)
+            pl.drop_arena = torch.empty(max(n, 1), **f32)
+            pl.drop_segs = K.rng_segments(segs)
+            for i, off, sh in views:
+                DM[i] = pl.drop_arena[off:off + math.prod(sh)].view(sh)
+        pl.DM = DM
         pl.graphs = {}
         lengths, V1, V2, K1, K2 = pl.lengths, pl.V1, pl.V2, pl.K1, pl.K2
         sp, XT, FA = pl.sp, pl.XT, pl.FA
@@ -348,8 +444,10 @@ class FreeRunningDecoder:
         Wqkv, bqkv = pl.Wqkv, pl.bqkv
         Wms, bms = pl.Wms, pl.bms
 
-        def prenets(x, out):
-            """the decoder prenets on the fed frame; the last layer writes `out`"""
+        def prenets(x, out, t):
+            """the decoder prenets on the fed frame; the last layer writes `out`.  Under
+            apply_dropout_on_inference row t of a dropping layer's mask is its `mul` epilogue
+            (the MultiSpeakerPreNet has none: DM[0] is None then)"""
             L = len(d.dec_prenet)
             if sp is not None:                             # multi_speaker_modules.py:27-32
                 ms = "decoder/prenet0"
@@ -362,7 +460,8 @@ class FreeRunningDecoder:
                 y, start = x, 0
             for i in range(start, L):
                 y = K.linear(y, P[f"decoder/prenet{i}/kernel"], P[f"decoder/prenet{i}/bias"],
-                             act="relu", out=out if i == L - 1 else None)
+                             act="relu", out=out if i == L - 1 else None,
+                             mul=None if DM[i] is None else DM[i][t])
 
         def head_step(h, t):
             """TransformerWrapper row t + OutputAndStopTokenTransparentWrapper projections:
@@ -437,7 +536,7 @@ class FreeRunningDecoder:
                 x = SMX[:, M * (r - nf):]
             else:
                 x = MEL[t - 1][:, M * (r - nf):]
-            prenets(x, REC0X[t][:, :p_w])
+            prenets(x, REC0X[t][:, :p_w], t)
             # the attention RNN on [prenet | c1 c2 | h0_{t-1}] against its whole kernel
             K.lstm_step_fwd(B=B, U=A, K=RXW, t=t, xproj=None,
                             bias=P["decoder/attention_lstm/bias"], rin=REC0X[t], W=W0,
@@ -597,6 +696,8 @@ class FreeRunningDecoder:
                 pl.pk = None
                 pl.err.zero_()
                 prepare()
+        if self.drop and self.last_path == "launches":
+            K.rng_fill_segments(pl.drop_arena, pl.drop_segs, self.seed)
         for a in range(0, Tm if self.last_path == "launches" else 0, self.check_every):
             b = min(Tm, a + self.check_every)
             self._steps(pl, a, b)
@@ -605,6 +706,8 @@ class FreeRunningDecoder:
                 if first >= 0:
                     steps = first + 1
                     break
+        if self.drop:
+            advance_seed(self.seed)       # the next run() draws other masks
         T_ = steps
         r, M = d.r, d.num_mels
         # copies, never views of the plan's buffers: the next run() on this shape zeroes and

@@ -393,6 +393,19 @@ def decode_persistent(**kw):
                "sat_decode_persistent")
 
 
+def decode_persistent_dropout(seed_dev: torch.Tensor, stream0: int, stream1: int, keep: float,
+                              **kw):
+    """sat_decode_persistent_dropout: sat_decode_persistent with the prenet dropout of
+    apply_dropout_on_inference drawn inside the kernel (``seed_dev``: the uint64 seed word in
+    device memory; ``stream0`` / ``stream1``: the Philox stream ids of the two prenet layers)."""
+    d = _lib.SatDecodePersistent()
+    for k, v in kw.items():
+        setattr(d, k, _p(v) if isinstance(v, torch.Tensor) or v is None else v)
+    _lib.check(_lib.load().sat_decode_persistent_dropout(
+        ctypes.byref(d), _p(seed_dev), stream0, stream1, keep, _stream()),
+        "sat_decode_persistent_dropout")
+
+
 def stop_check(stop: torch.Tensor, t: int, min_iters: int, state: torch.Tensor):
     """state[0] := t if (no earlier finish) and t > min_iters and all sigmoid(stop) > 0.5."""
     _lib.call("sat_stop_check", _p(stop), stop.stride(0), stop.shape[0], t, min_iters,

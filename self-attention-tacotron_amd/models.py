@@ -13,7 +13,8 @@ returns an ``EstimatorSpec``:
 * EVAL   -- ``loss`` of the validation decode (OneHotValidationHelper: softmax feedback, exactly
   T' steps with real attention; models/models.py:86-97) plus the teacher-forced
   ``loss_with_teacher`` metrics (models/models.py:208-235, 305-320); eval semantics (dropout off,
-  zoneout blend, BatchNorm moving statistics);
+  zoneout blend, BatchNorm moving statistics), except that ``apply_dropout_on_inference`` keeps
+  the decoder prenets' dropout on in EVAL and PREDICT (inference.py, DESIGN.md section 5a-2);
 * PREDICT -- free-running inference (BASELINE configs[4]; inference.FreeRunningDecoder: the
   stop-token helper + the KV-cached incremental decoder self-attention), returning the
   reference's predictions dict (models/models.py:252-277).
@@ -225,6 +226,10 @@ class DualSourceSelfAttentionTacotronModel:
         self._seed_offset = 1000003 * dp.rank()
         self._seed = seed + self._seed_offset
         self._eval_decoder = None
+        # apply_dropout_on_inference: the device seed word of every prenet mask drawn outside
+        # training (PREDICT / EVAL decodes and the teacher-forced eval passes share it; each
+        # draw advances it).  Starts from this replica's seed; not part of a checkpoint.
+        self._infer_seed_dev = None
         # event files: rank 0 alone writes (no other rank queues, launches or communicates)
         self.summaries = bool(summaries) and bool(model_dir) and dp.rank() == 0
         self._recorders: Dict[str, object] = {}
@@ -577,6 +582,32 @@ class DualSourceSelfAttentionTacotronModel:
                                       rank0_only=self._pending_rank0_only)
         return self._trainer
 
+    def _infer_seed(self) -> Optional[torch.Tensor]:
+        """The inference seed word (made on first use); None with the switch off, where no
+        decoder reads a seed and nothing is allocated."""
+        if not getattr(self.params, "apply_dropout_on_inference", False):
+            return None
+        if self._infer_seed_dev is None:
+            self._infer_seed_dev = torch.tensor([self._seed], dtype=torch.int64,
+                                                device=self.engine.device)
+        return self._infer_seed_dev
+
+    def _teacher_masks(self, batch):
+        """The masks of a teacher-forced pass outside training (models/models.py:134, :223 hand
+        ``apply_dropout_on_inference`` to the decoder): None with the switch off, else the
+        decoder prenet masks ``dec/prenet{l}`` [T', B, P_l] of the dropping layers, drawn from
+        the inference seed (which advances); everything else keeps eval semantics."""
+        if not getattr(self.params, "apply_dropout_on_inference", False):
+            return None
+        from .inference import advance_seed, draw_prenet_masks
+        B = batch["source"].shape[0]
+        Tp = batch["mel"].shape[1] // self.params.outputs_per_step
+        seed = self._infer_seed()
+        masks = draw_prenet_masks(self.engine.d, Tp, B,
+                                  1.0 - float(self.params.decoder_prenet_drop_rate), seed)
+        advance_seed(seed)
+        return masks
+
     def _predict(self, features) -> EstimatorSpec:
         """PREDICT (models/models.py:84-97, 252-277): free-running decode (inference.py) and
         the reference's predictions dict.  ``codes`` follows the fork's one-hot of the argmax
@@ -591,7 +622,8 @@ class DualSourceSelfAttentionTacotronModel:
                 batch["speaker_id"] = _to_device(features.speaker_id, dev, torch.int64)
             elif self.engine.d.spk_fixed < 0:     # speaker_for_synthesis replaces the ids
                 raise ValueError("use_speaker_embedding=True needs features.speaker_id")
-        out = FreeRunningDecoder(self.engine, max_iters=self.params.max_iters).run(batch)
+        out = FreeRunningDecoder(self.engine, max_iters=self.params.max_iters,
+                                 seed=self._infer_seed()).run(batch)
         mel = out["mel"]
         codes = torch.zeros_like(mel)
         codes.scatter_(2, mel.argmax(dim=2, keepdim=True), 1.0)       # tf.one_hot(argmax)
@@ -631,10 +663,12 @@ class DualSourceSelfAttentionTacotronModel:
                 raise ValueError(f"forced_alignment_attention must be a teacher_forcing kind: {k}")
         force_alignment_dual_source_attention_factory(hp)          # option checks
         with torch.no_grad():
-            first, _ = self.engine.forward(batch, None, training=False, need_grad=False)
+            first, _ = self.engine.forward(batch, self._teacher_masks(batch), training=False,
+                                           need_grad=False)
             a1 = first["alignment1"].permute(1, 0, 2).contiguous()    # [B, T', N]
             a2 = first["alignment2"].permute(1, 0, 2).contiguous()
-            dec = FreeRunningDecoder(self.engine, forced_alignments=(a1, a2), feed="softmax")
+            dec = FreeRunningDecoder(self.engine, forced_alignments=(a1, a2), feed="softmax",
+                                     seed=self._infer_seed())
             out = dec.run(batch)
         out["teacher_alignment1"] = a1.transpose(1, 2)
         out["teacher_alignment2"] = a2.transpose(1, 2)
@@ -656,7 +690,7 @@ class DualSourceSelfAttentionTacotronModel:
         from .inference import FreeRunningDecoder
         if self._eval_decoder is None:
             self._eval_decoder = FreeRunningDecoder(self.engine, helper="validation",
-                                                    feed="softmax")
+                                                    feed="softmax", seed=self._infer_seed())
         return self._eval_decoder.run(batch)
 
     def _eval(self, batch) -> EstimatorSpec:
@@ -673,7 +707,8 @@ class DualSourceSelfAttentionTacotronModel:
             else:
                 out = self.validation_pass(batch)
             l = self._loss_of(out["mel"], out["stop"], batch)
-            teach, _ = self.engine.forward(batch, None, training=False, need_grad=False)
+            teach, _ = self.engine.forward(batch, self._teacher_masks(batch), training=False,
+                                           need_grad=False)
         code_loss, done_loss = 0.1 * l[1:2], l[2:3]
         loss = code_loss + done_loss                                  # + regularization (0)
         metrics = {"code_loss": code_loss, "done_loss": done_loss,

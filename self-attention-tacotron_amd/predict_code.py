@@ -23,7 +23,8 @@ to fixed paths of its author's machine.
 
 CLI: ``python -m sat_amd.predict_code --source-data-root D --target-data-root D --checkpoint-dir D
 --selected-list-dir D --output-dir D [--checkpoint P] [--selected-list-filename test.csv]
-[--hparams S] [--hparam-json-file F] [--limit N] [--batch-size 1]``.
+[--hparams S] [--hparam-json-file F] [--limit N] [--batch-size 1] [--seed 1234]``
+(``--seed``: the prenet dropout masks under ``--hparams apply_dropout_on_inference=True``).
 """
 
 from __future__ import annotations
@@ -121,6 +122,8 @@ def main(argv=None) -> int:
     ap.add_argument("--hparam-json-file", default=None, help="JSON file of hyper-parameters")
     ap.add_argument("--limit", type=int, default=None, help="stop after this many utterances")
     ap.add_argument("--batch-size", type=int, default=1, help="utterances per predicted batch")
+    ap.add_argument("--seed", type=int, default=1234,
+                    help="seed of the prenet dropout masks (apply_dropout_on_inference=True)")
     args = ap.parse_args(argv)
     hp = create_hparams(args.hparam_json_file, args.hparams)
     print(hparams_debug_string(hp))
@@ -131,7 +134,7 @@ def main(argv=None) -> int:
           f"{os.path.join(args.selected_list_dir, args.selected_list_filename)}")
     src = [os.path.join(args.source_data_root, f"{k}.{hp.source_file_extension}") for k in keys]
     tgt = [os.path.join(args.target_data_root, f"{k}.{hp.target_file_extension}") for k in keys]
-    model = tacotron_model_factory(hp, args.checkpoint_dir, None)
+    model = tacotron_model_factory(hp, args.checkpoint_dir, None, seed=args.seed)
     done = predict_codes(model, predict_input_fn(hp, src, tgt, args.batch_size), args.output_dir,
                          hp, checkpoint_path=args.checkpoint, limit=args.limit)
     print(f"{len(done)} utterances written to {args.output_dir}")

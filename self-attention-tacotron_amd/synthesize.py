@@ -22,7 +22,8 @@ Not carried over: the PNG plots and the per-utterance prediction tfrecord of pre
 CLI: ``python -m sat_amd.synthesize --source-data-root D --target-data-root D --checkpoint-dir D
 --selected-list-dir D --output-dir D [--checkpoint P] [--selected-list-filename test.csv]
 [--hparams S] [--hparam-json-file F] [--no-wav] [--griffin-lim-iters 60] [--power 1.5]
-[--batch-size 1]``.
+[--batch-size 1] [--seed 1234]``.  ``--seed`` seeds the prenet dropout masks of a decode under
+``--hparams apply_dropout_on_inference=True`` (inference.py); the weights come from the checkpoint.
 """
 
 from __future__ import annotations
@@ -147,6 +148,9 @@ def main(argv=None) -> int:
     ap.add_argument("--power", type=float, default=1.5,
                     help="exponent on the linear magnitudes before Griffin-Lim")
     ap.add_argument("--batch-size", type=int, default=1, help="utterances per predicted batch")
+    ap.add_argument("--seed", type=int, default=1234,
+                    help="seed of the prenet dropout masks (apply_dropout_on_inference=True): "
+                         "the same seed and key list give the same files")
     args = ap.parse_args(argv)
     hp = create_hparams(args.hparam_json_file, args.hparams)
     print(hparams_debug_string(hp))
@@ -155,7 +159,7 @@ def main(argv=None) -> int:
     print(f"{len(keys)} keys from {listed}")
     src = [os.path.join(args.source_data_root, f"{k}.{hp.source_file_extension}") for k in keys]
     tgt = [os.path.join(args.target_data_root, f"{k}.{hp.target_file_extension}") for k in keys]
-    model = tacotron_model_factory(hp, args.checkpoint_dir, None)
+    model = tacotron_model_factory(hp, args.checkpoint_dir, None, seed=args.seed)
     preds = model.predict(predict_input_fn(hp, src, tgt, args.batch_size),
                           checkpoint_path=args.checkpoint)
     done = write_predictions(preds, args.output_dir, hp, wav=not args.no_wav,
