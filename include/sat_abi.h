@@ -383,6 +383,28 @@ int sat_decode_persistent(const SatDecodePersistent* a, void* stream);
  * it, sat_counter_add).  A separate kernel instantiation: sat_decode_persistent is unaffected. */
 int sat_decode_persistent_dropout(const SatDecodePersistent* a, const uint64_t* seed_ptr,
                                   uint64_t stream0, uint64_t stream1, float keep, void* stream);
+/* The same decode for the multi-speaker decoder (use_speaker_embedding with
+ * speaker_embedd_to_prenet: hparams.py vctk preset).  Prenet layer 0 is the MultiSpeakerPreNet
+ * (modules/multi_speaker_modules.py:27-32):
+ *   d0 = relu(x W_dense0 + b_dense0) + softsign(s_b W_sp + b_sp),  y0 = relu(d0 W_dense + b_dense)
+ * SatDecodePersistent carries the dense0 fold (Wzp = W_out[:, 80:160] W_dense0,
+ * bzp = b_out[80:160] W_dense0 + b_dense0, bp0 = b_dense0); spk0 is the softsign row of every
+ * utterance (constant over the decode, formed by the caller), Wd / bd the second dense.  One more
+ * phase and hand-off per step; everything after prenet layer 0 is the single-speaker decode.
+ * _spk_dropout: apply_dropout_on_inference -- only prenet layer 1 drops (the MultiSpeakerPreNet
+ * drops under is_training only), its mask the [T][B][128] draw on stream1 as above.
+ * Separate kernel instantiations: the two entries above are unaffected.  The scratch of
+ * sat_decode_persistent_scratch_bytes() serves all four. */
+typedef struct SatDecodeSpeaker {
+  const float* spk0;   /* [B][256] */
+  const float* Wd;     /* [256][256] */
+  const float* bd;     /* [256] */
+} SatDecodeSpeaker;
+int sat_decode_persistent_spk(const SatDecodePersistent* a, const SatDecodeSpeaker* s,
+                              void* stream);
+int sat_decode_persistent_spk_dropout(const SatDecodePersistent* a, const SatDecodeSpeaker* s,
+                                      const uint64_t* seed_ptr, uint64_t stream1, float keep,
+                                      void* stream);
 
 /* ---------------------------------------------------------------- (Zoneout)LSTM step
  * One time step of TF LSTMCell wrapped in ext tacotron2 ZoneoutLSTMCell,

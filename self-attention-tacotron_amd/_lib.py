@@ -163,6 +163,8 @@ SatDecodePersistent = _struct("SatDecodePersistent", """
     ptr:Wqku ptr:bqku ptr:bz ptr:Wms ptr:bms ptr:MS ptr:AL1 ptr:S2 ptr:SA_P ptr:state
     ptr:scratch i64:scratch_bytes ptr:err ptr:prof""")
 
+SatDecodeSpeaker = _struct("SatDecodeSpeaker", "ptr:spk0 ptr:Wd ptr:bd")
+
 
 class SatDecoderLoopFwd(ctypes.Structure):   # mirrors include/sat_abi.h
     _fields_ = [("attn", SatDecAttnFwd), ("lstm", SatDecLstmFwd), ("W1x", _P), ("b1", _P),
@@ -243,6 +245,10 @@ SIGNATURES = {
     "sat_decode_persistent": [ctypes.POINTER(SatDecodePersistent), _P],
     "sat_decode_persistent_dropout": [ctypes.POINTER(SatDecodePersistent), _P, _U64, _U64, _F,
                                       _P],
+    "sat_decode_persistent_spk": [ctypes.POINTER(SatDecodePersistent),
+                                  ctypes.POINTER(SatDecodeSpeaker), _P],
+    "sat_decode_persistent_spk_dropout": [ctypes.POINTER(SatDecodePersistent),
+                                          ctypes.POINTER(SatDecodeSpeaker), _P, _U64, _F, _P],
     "sat_zlstm_step_fwd": [ctypes.POINTER(SatLstmFwd), _P],
     "sat_zlstm_step_bwd": [ctypes.POINTER(SatLstmBwd), _P],
     "sat_attn_param_grad_rows": [_I32, _I32],

@@ -21,6 +21,8 @@
 // Per step t (group b, workgroup w owns LSTM units 8w..8w+7 and 8 / 4 / 32 dense columns):
 //   P1  z_{t-1} -> mel|stop of step t-1 (outputs, stop granule to every group) and the first
 //       prenet layer of step t (the fed frame is folded in: Wzp = W_out[:, fed] W_p0)
+//   P1b (multi-speaker kernels only, kSpk: one more all-gather) the second dense of the
+//       MultiSpeakerPreNet: P1 publishes d0 = relu(dense0) + speaker row, P1b its dense + ReLU
 //   P2  prenet layer 2                         P3  attention RNN (ZoneoutLSTM 256)
 //   P4  query layers of both attentions        P5  16 workgroups: energies of their memory
 //       positions + flash-style tile records (max, sum e, sum a~ e, partial contexts)
@@ -86,6 +88,9 @@ constexpr int kGroupFloats = oSA + 2 * kW * kSaRec;
 // after the groups: stop granules [2][8] (uint2), placement words [256], then the caches
 constexpr int64_t kZeroDwords = (int64_t)kG * kGroupFloats + 32 + 256;
 constexpr int64_t kCacheFloats = (int64_t)kG * kW * kRM * kRow;
+// behind the caches (nothing above moves): the kSpk kernels' hand-off of d0, the first dense of
+// the MultiSpeakerPreNet, [group][2 slots][256] tagged floats -- cleared with the hand-offs
+constexpr int64_t kD0Dwords = (int64_t)kG * 2 * kP0;
 
 __device__ __forceinline__ float4 fma4(float x, float4 w, float4 a) {
   return make_float4(fmaf(x, w.x, a.x), fmaf(x, w.y, a.y), fmaf(x, w.z, a.z), fmaf(x, w.w, a.w));
@@ -161,9 +166,23 @@ struct DropArgs<true> {
   float keep, on;            // keep probability, value of a surviving element (1 / keep)
 };
 
-template <bool kDrop>
+// The multi-speaker decoder (kSpk = true: use_speaker_embedding with speaker_embedd_to_prenet).
+// Prenet layer 0 is the MultiSpeakerPreNet (modules/multi_speaker_modules.py:27-32):
+//   d0 = relu(x W_dense0 + b_dense0) + softsign(s_b W_sp + b_sp),  y0 = relu(d0 W_dense + b_dense)
+// The softsign row is constant over the decode and comes in as spk0; Wzp / bzp / bp0 of
+// SatDecodePersistent carry the dense0 fold.  kSpk = false carries an empty struct: the
+// single-speaker kernels hold no trace of the extra phase.
+template <bool kSpk>
+struct SpkArgs {};
+template <>
+struct SpkArgs<true> {
+  SatDecodeSpeaker s;
+};
+
+template <bool kDrop, bool kSpk>
 __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersistent p,
-                                                                DropArgs<kDrop> args) {
+                                                                DropArgs<kDrop> args,
+                                                                SpkArgs<kSpk> spk) {
   const int g = blockIdx.x % kG, w = blockIdx.x / kG;
   if (g >= p.B) return;   // no utterance: no partner outside this group
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -206,6 +225,11 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
   __shared__ float hdr[8], scs1[kAW], scs2[kAW], sa_s[2 * kRM], sa_pe[2 * kRM], mine[4];
   __shared__ float cbzp[8], cbp0[8], cbms[8], cbp1[4], cbqku[32], cbz[8];
   __shared__ int flag;
+  // kSpk: the gathered d0 row (its own buffer: xy0 is refilled by P2's gather while slower waves
+  // of this workgroup may still be reading d0), the speaker row and dense bias of own columns
+  // (never referenced, and so never allocated, in the kSpk = false kernels)
+  __shared__ __attribute__((aligned(16))) float xd0[kP0];
+  __shared__ float cspk[8], cbd[8];
 
   // ---------------------------------------------------------------- one-time loads
   const int uu = 8 * w + wave;   // the LSTM unit of this wave (all three LSTMs)
@@ -242,6 +266,15 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
     wq[i] = p.Wq[(size_t)k * kQ + cq];
 #pragma unroll
     for (int j = 0; j < 4; ++j) wk[j][i] = p.Wqku[(size_t)k * kQKU + 32 * w + 4 * wave + j];
+  }
+  // kSpk: the d0 slots of this group (behind every group's caches) and column cpre of W_dense,
+  // the layout of wzp / wq
+  float* d0s = nullptr;
+  float wd[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (kSpk) {
+    d0s = scr + kZeroDwords + kCacheFloats + (size_t)g * 2 * kP0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) wd[i] = spk.s.Wd[(size_t)(lane + 64 * i) * kP0 + cpre];
   }
   // attention: K1 + b1 / K2 slices of this lane's position (32 lanes per position)
   // (one wave per position, lane = energy dims lane + 64 j)
@@ -287,6 +320,10 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
     const int cm = w + 32 * tid;
     cbms[tid] = (tid < 6 && cm <= kMR) ? p.bms[cm] : 0.f;
     if (tid < 4) cbp1[tid] = p.bp1[4 * w + tid];
+    if constexpr (kSpk) {
+      cspk[tid] = spk.s.spk0[(size_t)g * kP0 + 8 * w + tid];
+      cbd[tid] = spk.s.bd[8 * w + tid];
+    }
   }
   if (tid < 32) cbqku[tid] = p.bqku[32 * w + tid];
   __syncthreads();
@@ -333,8 +370,9 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
     // kDrop: this wave's word of the first prenet mask, the value sat_rng_fill writes at element
     // (t B + g) 256 + cpre of the step-major [T][B][256] tensor -- formed before the gather, so
     // it runs while z_{t-1} is still in flight (arithmetic only: no barrier, no memory access)
+    // (kSpk: layer 0 is the MultiSpeakerPreNet, which drops under is_training only -- no dm0)
     float dm0 = 1.f;
-    if constexpr (kDrop)
+    if constexpr (kDrop && !kSpk)
       dm0 = rng_mask_value(((uint64_t)t * p.B + g) * kP0 + cpre, args.stream0, dkey, args.keep,
                            args.on);
     if (t > 0) {
@@ -366,10 +404,26 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
         a = cbp0[wave];   // the go frame (zeros)
       }
       a = fmaxf(a, 0.f);
-      if constexpr (kDrop) a *= dm0;   // dropout after the ReLU (PreNet)
-      if (lane == 0) stcx(xl, R, oY0 + s * kP0 + cpre, tagf(a, bt));
+      if constexpr (kSpk) {
+        // d0 = relu(dense0) + the utterance's softsign row: handed on to P1b
+        a += cspk[wave];
+        if (lane == 0) stcx(xl, rsrc(d0s), s * kP0 + cpre, tagf(a, bt));
+      } else {
+        if constexpr (kDrop) a *= dm0;   // dropout after the ReLU (PreNet)
+        if (lane == 0) stcx(xl, R, oY0 + s * kP0 + cpre, tagf(a, bt));
+      }
     }
     TP(3)
+    // ================================================= P1b (kSpk): y0 = relu(d0 W_dense + b_dense)
+    if constexpr (kSpk) {
+      gather<1>(rsrc(d0s), s * kP0 / 4, kP0 / 4, reinterpret_cast<float4*>(xd0), bt, p.err);
+      lds_barrier();
+      float a = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a = fmaf(xd0[lane + 64 * i], wd[i], a);
+      a = fmaxf(wave_sum_dpp(a) + cbd[wave], 0.f);
+      if (lane == 0) stcx(xl, R, oY0 + s * kP0 + cpre, tagf(a, bt));
+    }
     // ================================================= P2: prenet layer 2
     float dm1 = 1.f;   // kDrop: element (t B + g) 128 + cp1 of the [T][B][128] mask, as above
     if constexpr (kDrop) {
@@ -755,14 +809,21 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
 
 using namespace sat;
 
+// The entries live in two modules built from this one source: the single-speaker pair here, the
+// multi-speaker pair in decode_persistent_spk.hip (which defines SAT_DP_SPK and includes this
+// file).  One module holding all four kernels compiles the single-speaker pair to another
+// instruction stream than the module without the multi-speaker pair does; apart, adding the
+// kSpk kernels leaves the existing two exactly as they were (`make asm`).
+#ifndef SAT_DP_SPK
 extern "C" int64_t sat_decode_persistent_scratch_bytes(void) {
-  return (kZeroDwords + kCacheFloats) * 4;
+  return (kZeroDwords + kCacheFloats + kD0Dwords) * 4;
 }
+#endif
 
-// Argument checks, co-residency test, scratch clear and launch shared by the two entries.
-template <bool kDrop>
+// Argument checks, co-residency test, scratch clear and launch shared by the four entries.
+template <bool kDrop, bool kSpk>
 static int launch_decode(const SatDecodePersistent* a, const DropArgs<kDrop>& args,
-                         void* stream) {
+                         const SpkArgs<kSpk>& spk, void* stream) {
   SAT_CHECK_ARG(a && a->B >= 1 && a->B <= kG && a->N >= 1 && a->N <= kNM && a->T >= 1 &&
                     a->T <= kW * kRM,
                 "sat_decode_persistent: B <= 8, N <= 256, T <= 512 (got B=%d N=%d T=%d)",
@@ -781,9 +842,8 @@ static int launch_decode(const SatDecodePersistent* a, const DropArgs<kDrop>& ar
   int dev = 0, cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_persistent_kernel<kDrop>, kTh,
-                                                   0) !=
-          hipSuccess) {
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_persistent_kernel<kDrop, kSpk>,
+                                                   kTh, 0) != hipSuccess) {
     set_error("sat_decode_persistent: device query failed");
     return SAT_ERR_HIP;
   }
@@ -792,17 +852,31 @@ static int launch_decode(const SatDecodePersistent* a, const DropArgs<kDrop>& ar
     return SAT_ERR_UNSUPPORTED;
   }
   hipStream_t s = as_stream(stream);
-  if (zero_ranges(s, a->scratch, kZeroDwords, a->err, 1) != hipSuccess) {
+  // the d0 slots (behind the caches) carry tagged words too: cleared like the other hand-offs
+  float* d0 = reinterpret_cast<float*>(a->scratch) + kZeroDwords + kCacheFloats;
+  if (zero_ranges(s, a->scratch, kZeroDwords, a->err, 1, kSpk ? d0 : nullptr, kD0Dwords) !=
+      hipSuccess) {
     set_error("sat_decode_persistent: scratch clear failed");
     return SAT_ERR_HIP;
   }
-  hipLaunchKernelGGL(decode_persistent_kernel<kDrop>, dim3(kG * kW), dim3(kTh), 0, s, *a, args);
+  hipLaunchKernelGGL((decode_persistent_kernel<kDrop, kSpk>), dim3(kG * kW), dim3(kTh), 0, s, *a,
+                     args, spk);
   SAT_LAUNCH_CHECK("sat_decode_persistent");
   return SAT_OK;
 }
 
+static void drop_args(const uint64_t* seed_ptr, uint64_t stream0, uint64_t stream1, float keep,
+                      DropArgs<true>* args) {
+  args->seed = seed_ptr;
+  args->stream0 = stream0;
+  args->stream1 = stream1;
+  args->keep = keep;
+  args->on = (float)(1.0 / (double)keep);
+}
+
+#ifndef SAT_DP_SPK
 extern "C" int sat_decode_persistent(const SatDecodePersistent* a, void* stream) {
-  return launch_decode<false>(a, DropArgs<false>{}, stream);
+  return launch_decode<false, false>(a, DropArgs<false>{}, SpkArgs<false>{}, stream);
 }
 
 extern "C" int sat_decode_persistent_dropout(const SatDecodePersistent* a, const uint64_t* seed_ptr,
@@ -812,10 +886,31 @@ extern "C" int sat_decode_persistent_dropout(const SatDecodePersistent* a, const
   SAT_CHECK_ARG(keep > 0.f, "sat_decode_persistent_dropout: keep must be > 0 (got %g)",
                 (double)keep);
   DropArgs<true> args;
-  args.seed = seed_ptr;
-  args.stream0 = stream0;
-  args.stream1 = stream1;
-  args.keep = keep;
-  args.on = (float)(1.0 / (double)keep);
-  return launch_decode<true>(a, args, stream);
+  drop_args(seed_ptr, stream0, stream1, keep, &args);
+  return launch_decode<true, false>(a, args, SpkArgs<false>{}, stream);
 }
+#else
+
+extern "C" int sat_decode_persistent_spk(const SatDecodePersistent* a, const SatDecodeSpeaker* sp,
+                                         void* stream) {
+  SAT_CHECK_ARG(a && sp && sp->spk0 && sp->Wd && sp->bd, "sat_decode_persistent_spk: null pointer");
+  SpkArgs<true> spk;
+  spk.s = *sp;
+  return launch_decode<false, true>(a, DropArgs<false>{}, spk, stream);
+}
+
+extern "C" int sat_decode_persistent_spk_dropout(const SatDecodePersistent* a,
+                                                 const SatDecodeSpeaker* sp,
+                                                 const uint64_t* seed_ptr, uint64_t stream1,
+                                                 float keep, void* stream) {
+  SAT_CHECK_ARG(a && sp && sp->spk0 && sp->Wd && sp->bd && seed_ptr,
+                "sat_decode_persistent_spk_dropout: null pointer");
+  SAT_CHECK_ARG(keep > 0.f, "sat_decode_persistent_spk_dropout: keep must be > 0 (got %g)",
+                (double)keep);
+  DropArgs<true> args;
+  drop_args(seed_ptr, 0, stream1, keep, &args);   // stream0: layer 0 never drops here
+  SpkArgs<true> spk;
+  spk.s = *sp;
+  return launch_decode<true, true>(a, args, spk, stream);
+}
+#endif

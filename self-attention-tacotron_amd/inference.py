@@ -50,7 +50,8 @@ the MultiSpeakerPreNet (layer 0 under ``speaker_embedd_to_prenet``) drops under 
 only and so stays clean.  The launch path fills the masks of the whole decode in one
 ``sat_rng_fill_segments`` launch before the loop (outside any captured graph) and multiplies row
 t in as the prenet products' ``mul`` epilogue; the one-launch decode draws the same words inside
-the kernel (``sat_decode_persistent_dropout``).  Every ``run()`` advances the seed by one on the
+the kernel (``sat_decode_persistent_dropout``; ``sat_decode_persistent_spk_dropout`` for the
+multi-speaker decoder, where only layer 1 draws).  Every ``run()`` advances the seed by one on the
 device (``sat_counter_add``); the seed is not part of a checkpoint.
 
 Every arithmetic op is a libsat_hip kernel; torch allocates, views and copies.
@@ -136,9 +137,11 @@ class FreeRunningDecoder:
     ``check_every`` = decoder steps between host reads of the device-side finished flag (and
     the steps per captured graph when ``graphs=True``).
     ``persistent``: run the whole decode as ONE launch (``sat_decode_persistent``) -- None picks
-    it whenever the shape allows (mel feedback, no forced alignments, single speaker, the
-    LJSpeech decoder dimensions, B <= 8, N <= 256, T' <= 512), True requires it, False keeps the
-    per-step launches.
+    it whenever the shape allows (mel feedback, no forced alignments, the LJSpeech / VCTK decoder
+    dimensions -- single speaker, or the speaker embedding fed to the prenet only
+    (``speaker_embedd_to_prenet``; not ``speaker_embedd_to_decoder``) --, no transition agent or
+    cumulative weights, B <= 8, N <= 256, T' <= 512), True requires it, False keeps the per-step
+    launches.
     ``seed``: the seed of the prenet masks under ``apply_dropout_on_inference`` -- an int (a
     device word of its own is made) or a one-element int64 device tensor the caller shares
     between decoders; every ``run()`` advances it by one.  Unused with the switch off.  With the
@@ -220,7 +223,7 @@ class FreeRunningDecoder:
         d, hp = self.d, self.hp
         dims = dict(dec_prenet=(256, 128), feed=80, att_rnn=256, m1=256, m2=32, d1=224, d2=32,
                     loc_k=10, loc_f=5, dec=256, dsa=256, dec_heads=2, dec_hops=1, num_mels=80, r=2,
-                    att1="forward", att2="additive", multi_speaker=False)
+                    att1="forward", att2="additive")
         for k, v in dims.items():
             if getattr(d, k) != v:
                 return f"{k}={getattr(d, k)!r}, needs {v!r}"
@@ -261,13 +264,15 @@ class FreeRunningDecoder:
         """Fold the fed frame into the first prenet layer and the value / output projection /
         transform products into the cached rows (exact algebra, fp32 products):
         Wzp = W_out[:, fed] W_p0, bzp = b_out[fed] W_p0 + b_p0;
-        Wqku = [W_q | W_k | W_v,h (W_o,h W_t)], bz = (b_v W_o + b_o) W_t + b_t."""
+        Wqku = [W_q | W_k | W_v,h (W_o,h W_t)], bz = (b_v W_o + b_o) W_t + b_t.
+        Multi-speaker: W_p0 / b_p0 are dense0 of the MultiSpeakerPreNet."""
         P, d, pk = self.m.P, self.d, pl.pk
         M, r = d.num_mels, d.r
         fed = slice(M * (r - self.hp.n_feed_frame), M * r)
-        Wp0 = P["decoder/prenet0/kernel"]
+        p0 = "decoder/prenet0/dense0" if d.multi_speaker else "decoder/prenet0"
+        Wp0 = P[f"{p0}/kernel"]
         K.gemm(pl.Wms[:, fed], Wp0, pk["Wzp"])
-        K.gemm(pl.bms[fed].unsqueeze(0), Wp0, pk["bzp"], bias=P["decoder/prenet0/bias"])
+        K.gemm(pl.bms[fed].unsqueeze(0), Wp0, pk["bzp"], bias=P[f"{p0}/bias"])
         pk["Wq"][:, :d.d1].copy_(P["decoder/attention1/query_layer/kernel"])
         pk["Wq"][:, d.d1:].copy_(P["decoder/attention2/query_layer/kernel"])
         mh, sc = "decoder/self_attention0/mha", "decoder/self_attention0"
@@ -292,17 +297,29 @@ class FreeRunningDecoder:
         a1, a2 = "decoder/attention1", "decoder/attention2"
         self._pack_persistent(pl)
         pk = pl.pk
-        launch = K.decode_persistent
-        if self.drop:       # single speaker (_why_not): both prenet layers drop
+        p0 = "decoder/prenet0"
+        if d.multi_speaker:
+            # layer 0 = MultiSpeakerPreNet: pl.sp is the softsign row _prepare formed for both
+            # paths; under the dropout switch only layer 1 drops (prenet_drops)
+            p0, ms = "decoder/prenet0/dense0", "decoder/prenet0/dense"
+            spk = (pl.sp, P[f"{ms}/kernel"], P[f"{ms}/bias"])
+            if self.drop:
+                launch = functools.partial(K.decode_persistent_spk_dropout, *spk, self.seed,
+                                           DROP_STREAM0 + 1, self.keep)
+            else:
+                launch = functools.partial(K.decode_persistent_spk, *spk)
+        elif self.drop:     # both prenet layers drop
             launch = functools.partial(K.decode_persistent_dropout, self.seed, DROP_STREAM0,
                                        DROP_STREAM0 + 1, self.keep)
+        else:
+            launch = K.decode_persistent
         launch(
             B=pl.B, N=pl.N, T=Tm, min_iters=self.min_iters,
             stop_mode=1 if self.helper == "stop_token" else 0,
             zc=hp.zoneout_factor_cell, zh=hp.zoneout_factor_output, u=0.5,
             scale=1.0 / math.sqrt(d.dsa // d.dec_heads),
             lengths=pl.lengths, K1=pl.K1, V1=pl.V1, K2=pl.K2, V2=pl.V2,
-            Wzp=pk["Wzp"], bzp=pk["bzp"], bp0=P["decoder/prenet0/bias"],
+            Wzp=pk["Wzp"], bzp=pk["bzp"], bp0=P[f"{p0}/bias"],
             Wp1=P["decoder/prenet1/kernel"], bp1=P["decoder/prenet1/bias"],
             W0=P["decoder/attention_lstm/kernel"], b0=P["decoder/attention_lstm/bias"],
             Wq=pk["Wq"], b1=P[f"{a1}/attention_bias"], v1=P[f"{a1}/attention_variable"],

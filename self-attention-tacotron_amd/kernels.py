@@ -406,6 +406,37 @@ def decode_persistent_dropout(seed_dev: torch.Tensor, stream0: int, stream1: int
         "sat_decode_persistent_dropout")
 
 
+def _decode_speaker(spk0: torch.Tensor, Wd: torch.Tensor, bd: torch.Tensor):
+    s = _lib.SatDecodeSpeaker()
+    s.spk0, s.Wd, s.bd = _p(spk0), _p(Wd), _p(bd)
+    return s
+
+
+def decode_persistent_spk(spk0: torch.Tensor, Wd: torch.Tensor, bd: torch.Tensor, **kw):
+    """sat_decode_persistent_spk: sat_decode_persistent for the multi-speaker decoder (prenet
+    layer 0 = MultiSpeakerPreNet).  ``spk0`` [B, 256]: the softsign speaker row of every
+    utterance; ``Wd`` / ``bd``: the second dense; Wzp / bzp / bp0 carry the dense0 fold."""
+    d = _lib.SatDecodePersistent()
+    for k, v in kw.items():
+        setattr(d, k, _p(v) if isinstance(v, torch.Tensor) or v is None else v)
+    s = _decode_speaker(spk0, Wd, bd)
+    _lib.check(_lib.load().sat_decode_persistent_spk(ctypes.byref(d), ctypes.byref(s), _stream()),
+               "sat_decode_persistent_spk")
+
+
+def decode_persistent_spk_dropout(spk0: torch.Tensor, Wd: torch.Tensor, bd: torch.Tensor,
+                                  seed_dev: torch.Tensor, stream1: int, keep: float, **kw):
+    """sat_decode_persistent_spk_dropout: the same under apply_dropout_on_inference -- only
+    prenet layer 1 drops (``stream1``: the Philox stream id of its mask)."""
+    d = _lib.SatDecodePersistent()
+    for k, v in kw.items():
+        setattr(d, k, _p(v) if isinstance(v, torch.Tensor) or v is None else v)
+    s = _decode_speaker(spk0, Wd, bd)
+    _lib.check(_lib.load().sat_decode_persistent_spk_dropout(
+        ctypes.byref(d), ctypes.byref(s), _p(seed_dev), stream1, keep, _stream()),
+        "sat_decode_persistent_spk_dropout")
+
+
 def stop_check(stop: torch.Tensor, t: int, min_iters: int, state: torch.Tensor):
     """state[0] := t if (no earlier finish) and t > min_iters and all sigmoid(stop) > 0.5."""
     _lib.call("sat_stop_check", _p(stop), stop.stride(0), stop.shape[0], t, min_iters,
