@@ -50,7 +50,9 @@ extern "C" {
  * signature touched -- so a binding of 13 without them reads a library with them correctly.
  * Still 13 with the L2 regulariser (sat_l2_regularize, sat_workspace_l2): two new symbols.
  * Still 13 with the resampler (sat_resample): one new symbol.
- * Still 13 with the VQ-code kernels (sat_codes_batch, sat_codes_argmax): two new symbols. */
+ * Still 13 with the VQ-code kernels (sat_codes_batch, sat_codes_argmax): two new symbols.
+ * Still 13 with the synthesis figures (sat_figure_render, SatFigure, SatFigurePanel): one new
+ * symbol and two new structs. */
 #define SAT_ABI_VERSION 13
 
 /* ---------------------------------------------------------------- library */
@@ -1056,6 +1058,64 @@ int sat_image_render(const float* src, int64_t src_n, const int64_t* base, const
                      const int32_t* cols, int64_t col_stride, int32_t n_images, int32_t Rmax,
                      int32_t Cmax, const int32_t* rows_host, const int32_t* cols_host,
                      const float* minmax, uint8_t* canvas, void* stream);
+
+/* ---------------------------------------------------------------- synthesis figures
+ * One colour figure per utterance (the reference's plot_predictions, modules/metrics.py:13-53;
+ * sat_amd/plots.py writes them as PNG files): n_panel panels stacked top to bottom, each a
+ * nearest-neighbour resampling of one crop into a box of Hp x Wp pixels, mapped through a colour
+ * table, with a colour bar strip at its right.  ONE launch composes all n_fig figures.
+ *
+ * Panel k of figure f is panels[f * n_panel + k] (a DEVICE array).  Its crop is addressed as
+ * sat_image_render addresses one: element (r, c) is src[base + c * col_stride + r], the crop is
+ * rows x cols (<= 0 is an empty crop), reads outside src[0, src_n) give 0.  minmax points at the
+ * crop's {lo, hi} pair, as sat_image_minmax wrote it.  Panels of one figure may name different
+ * source tensors.
+ *
+ * Geometry, the same for every figure of the launch: margin m, colour bar width cb,
+ *   Hfig = n_panel * Hp + (n_panel + 1) * m,   Wfig = Wp + cb + 3 * m,
+ * canvas uint8 [n_fig][Hfig][Wfig][3] (contiguous; ANY byte alignment).  Panel k's box has its
+ * top left pixel at (m + k * (Hp + m), m), its colour bar strip at column 2 * m + Wp.
+ *   box pixel (y, x):  r = ((2 * (Hp - 1 - y) + 1) * rows) / (2 * Hp)    (source row 0 at the bottom)
+ *                      c = ((2 * x + 1) * cols) / (2 * Wp)               (integer division)
+ *                      colour = lut[table][q(src(r, c))], q of sat_image_render with the panel's
+ *                      {lo, hi}; an empty crop gives lut[table][0] everywhere
+ *   strip pixel (y, .): lut[table][255 - (255 * y) / (Hp - 1)]  (entry 0 when Hp == 1)
+ *   every other pixel:  background (bytes R, G, B = background & 255, >> 8 & 255, >> 16 & 255)
+ * lut is uint8 [n_tables][256][3]; a device `table` outside 0..n_tables-1 is clamped into it.
+ * Every canvas byte is written exactly once by plain stores (no memset, no atomics): two runs give
+ * the same bytes.  The grid is a function of the geometry alone.
+ *
+ * panels_host (nullable) is a host copy of the table for callers that have one; the per-panel
+ * checks below need it.  Refused with SAT_ERR_ARGUMENT before anything is launched: a null
+ * descriptor, panels, lut or canvas; a negative n_fig, n_panel, m or cb; Hp or Wp < 1;
+ * n_fig * n_panel > 65535; n_tables outside 1..8 (the tables are staged in LDS); lut not 4-byte
+ * aligned; a figure of 2^31 pixels or more; and per panel of panels_host: a null or not 4-byte
+ * aligned src or minmax, a negative src_n or col_stride, a table outside 0..n_tables-1.
+ * n_fig == 0 or n_panel == 0 (with m == 0: no canvas byte) launches nothing. */
+typedef struct SatFigurePanel {
+  const float* src;
+  int64_t src_n;
+  int64_t base;
+  int64_t col_stride;
+  const float* minmax;
+  int32_t rows, cols;
+  int32_t table;
+  int32_t pad0;
+} SatFigurePanel;
+
+typedef struct SatFigure {
+  int32_t n_fig, n_panel;
+  int32_t Hp, Wp;
+  int32_t margin, cbar;
+  int32_t n_tables;
+  uint32_t background;
+  const SatFigurePanel* panels;       /* device [n_fig * n_panel] */
+  const SatFigurePanel* panels_host;  /* host copy, nullable */
+  const uint8_t* lut;                 /* device [n_tables][256][3] */
+  uint8_t* canvas;                    /* device [n_fig][Hfig][Wfig][3] */
+} SatFigure;
+
+int sat_figure_render(const SatFigure* d, void* stream);
 
 /* ---------------------------------------------------------------- audio front end
  * Waveform to log-mel targets: Audio.melspectrogram (utils/audio.py:51-73) with librosa 0.6 stft

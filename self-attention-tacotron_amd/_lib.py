@@ -203,6 +203,16 @@ SatGriffinLim = _struct("SatGriffinLim", """
     f32:momentum i32:pad0 ptr:mag ptr:init_phase ptr:frames ptr:frames_host ptr:window
     ptr:twiddle ptr:wav ptr:scratch i64:scratch_bytes""")
 
+SatFigurePanel = _struct("SatFigurePanel", """
+    ptr:src i64:src_n i64:base i64:col_stride ptr:minmax i32:rows i32:cols i32:table i32:pad0""")
+
+
+class SatFigure(ctypes.Structure):          # mirrors include/sat_abi.h
+    _fields_ = [("n_fig", _I32), ("n_panel", _I32), ("Hp", _I32), ("Wp", _I32), ("margin", _I32),
+                ("cbar", _I32), ("n_tables", _I32), ("background", ctypes.c_uint32),
+                ("panels", _P), ("panels_host", _P), ("lut", _P), ("canvas", _P)]
+
+
 # name -> argtypes (restype is int for all but sat_last_error_string)
 SIGNATURES = {
     "sat_version": [],
@@ -303,6 +313,7 @@ SIGNATURES.update({
     "sat_griffin_lim": [ctypes.POINTER(SatGriffinLim), _P],
     "sat_codes_batch": [_P, _I64, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
     "sat_codes_argmax": [_P, _I64, _I32, _I32, _P, _P, _I64, _P],
+    "sat_figure_render": [ctypes.POINTER(SatFigure), _P],
 })
 
 RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),

@@ -1170,6 +1170,49 @@ def image_render(src, base, rows, cols, col_stride, minmax, canvas, rows_host=No
     _lib.call("sat_image_render", *args, _p(minmax), _p(canvas), _stream())
 
 
+# ---- synthesis figures (csrc/figure.hip; sat_amd/plots.py)
+def figure_panels(rows):
+    """The host descriptor table of ``figure_render``: ``rows`` are (src, base, rows, cols,
+    col_stride, table, minmax) per panel, figure-major -- ``src`` a contiguous float32 device
+    tensor, ``minmax`` a float32 device tensor whose first two elements are the crop's {lo, hi}."""
+    table = (_lib.SatFigurePanel * max(len(rows), 1))()
+    for p, (src, base, r, c, col_stride, tab, minmax) in zip(table, rows):
+        if src.dtype != torch.float32 or not src.is_contiguous():
+            raise ValueError("figure source: a contiguous float32 tensor")
+        if minmax.dtype != torch.float32 or minmax.numel() < 2:
+            raise ValueError("figure panel: minmax must hold two float32 values")
+        p.src, p.src_n, p.base, p.col_stride = _p(src), src.numel(), int(base), int(col_stride)
+        p.minmax, p.rows, p.cols, p.table = _p(minmax), int(r), int(c), int(tab)
+    return table
+
+
+def figure_render(panels_host, panels, lut, canvas, Hp, Wp, margin, cbar, background=0xFFFFFF):
+    """Composes ``canvas`` (uint8 [n_fig, Hfig, Wfig, 3], dense, at any byte offset of its
+    storage) in one launch; see include/sat_abi.h.  ``panels_host``: ``figure_panels(...)``;
+    ``panels``: a uint8 device tensor holding the same bytes; ``lut`` uint8 [n_tables, 256, 3]."""
+    if canvas.dtype != torch.uint8 or canvas.dim() != 4 or canvas.shape[3] != 3 \
+            or not canvas.is_contiguous():
+        raise ValueError("figure_render: canvas must be a dense uint8 [n_fig, Hfig, Wfig, 3]")
+    if lut.dtype != torch.uint8 or lut.dim() != 3 or tuple(lut.shape[1:]) != (256, 3) \
+            or not lut.is_contiguous():
+        raise ValueError("figure_render: lut must be a contiguous uint8 [n_tables, 256, 3]")
+    n_fig, Hfig, Wfig = (int(s) for s in canvas.shape[:3])
+    Hp, Wp, margin, cbar = int(Hp), int(Wp), int(margin), int(cbar)
+    if Hp < 1 or margin < 0 or (Hfig - margin) % (Hp + margin) or Wfig != Wp + cbar + 3 * margin:
+        raise ValueError(f"figure_render: a canvas of {Hfig} x {Wfig} pixels does not fit boxes of "
+                         f"{Hp} x {Wp}, margin {margin}, colour bar {cbar}")
+    n_panel = (Hfig - margin) // (Hp + margin)
+    size = ctypes.sizeof(_lib.SatFigurePanel)
+    if len(panels_host) < n_fig * n_panel or panels.dtype != torch.uint8 \
+            or not panels.is_contiguous() or panels.numel() < n_fig * n_panel * size:
+        raise ValueError("figure_render: one panel descriptor per figure and panel")
+    d = _lib.SatFigure(n_fig=n_fig, n_panel=n_panel, Hp=Hp, Wp=Wp, margin=margin, cbar=cbar,
+                       n_tables=int(lut.shape[0]), background=int(background) & 0xFFFFFF,
+                       panels=_p(panels), panels_host=ctypes.addressof(panels_host),
+                       lut=_p(lut), canvas=_p(canvas))
+    _lib.check(_lib.load().sat_figure_render(ctypes.byref(d), _stream()), "sat_figure_render")
+
+
 # ---- audio front end and vocoder (csrc/audio.hip, trim.hip, resample.hip, vocoder.hip;
 #      sat_amd/audio.py).  Only dtypes and buffer sizes are checked here: what an entry refuses,
 #      it refuses itself.

@@ -630,7 +630,12 @@ class DualSourceSelfAttentionTacotronModel:
         preds = {"id": features.id, "key": features.key, "codes": codes, "mel": mel,
                  "stop_token": out["stop"], "alignment": out["alignment1"],
                  "alignment2": out["alignment2"], "source": features.source,
-                 "text": getattr(features, "text", None)}
+                 "text": getattr(features, "text", None),
+                 # what the plot and the prediction record of a synthesis crop by and compare
+                 # with (predict_mel.py:50-53); absent where the features carry no target
+                 "source_length": features.source_length,
+                 "ground_truth_mel": getattr(features, "mel", None),
+                 "ground_truth_mel_length": getattr(features, "target_length", None)}
         # decoder self-attention alignments (per hop, per head, transposed as :108-109), then
         # the encoder's (alignment5..8)
         dec = [a[:, h].transpose(1, 2) for a in out["decoder_self_alignments"]

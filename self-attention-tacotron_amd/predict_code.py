@@ -10,7 +10,10 @@ per utterance
   codes, codes_length, codes_width, ground_truth_codes, ground_truth_codes_length, text, source,
   source_length``;
 * ``<key>.txt`` (the text), ``<key>.preds.txt`` and ``<key>.truth.txt`` (blank-joined code indices
-  and a newline): what postprocess_vqcodes.py:81-97 derives from that record.
+  and a newline): what postprocess_vqcodes.py:81-97 derives from that record;
+* ``<key>.png`` (``plots=True``, ``--plots``; off by default): the two alignments, the decoder
+  self-attention heads, the true and the predicted one-hot frames as one colour figure
+  (``sat_amd.plots``, composed on the GPU by csrc/figure.hip).
 
 The indices and the one-hot frames of a batch come from ONE ``sat_codes_argmax`` launch over the
 decoder's raw outputs (``predictions["mel"]``; ties to the lowest index, as ``tf.argmax``).  The
@@ -23,7 +26,7 @@ to fixed paths of its author's machine.
 
 CLI: ``python -m sat_amd.predict_code --source-data-root D --target-data-root D --checkpoint-dir D
 --selected-list-dir D --output-dir D [--checkpoint P] [--selected-list-filename test.csv]
-[--hparams S] [--hparam-json-file F] [--limit N] [--batch-size 1] [--seed 1234]``
+[--hparams S] [--hparam-json-file F] [--limit N] [--batch-size 1] [--seed 1234] [--plots]``
 (``--seed``: the prenet dropout masks under ``--hparams apply_dropout_on_inference=True``).
 """
 
@@ -50,9 +53,11 @@ def _codes_line(index) -> str:
 
 
 def write_code_predictions(pairs: Iterable, output_dir: str, hparams,
-                           limit: Optional[int] = None, min_iters: int = MIN_ITERS) -> List[str]:
+                           limit: Optional[int] = None, min_iters: int = MIN_ITERS,
+                           plots: bool = False, plot_options: Optional[dict] = None) -> List[str]:
     """Writes the files of every predicted batch (see the module docstring) and returns the keys
-    in the order written; stops after ``limit`` utterances when given."""
+    in the order written; stops after ``limit`` utterances when given.  ``plots``: also
+    ``<key>.png`` (``plots.write_plots``; ``plot_options`` its geometry)."""
     from . import kernels as K
     os.makedirs(output_dir, exist_ok=True)
     C, r = int(hparams.num_mels), int(hparams.outputs_per_step)
@@ -67,11 +72,21 @@ def write_code_predictions(pairs: Iterable, output_dir: str, hparams,
             raise ValueError(f"{len(keys)} keys for {B} predicted utterances")
         frames = stop_frames(p["stop_token"], r, T, min_iters)
         index, onehot = K.codes_argmax(raw.contiguous(), onehot=True)
+        truth_index, offsets = np.asarray(features.code_index), np.asarray(features.offsets)
+        if plots and (limit is None or len(written) < limit):
+            from . import plots as P
+            n_truth = np.diff(offsets[:B + 1]).astype(np.int64)
+            dense = np.zeros((B, max(int(n_truth.max()), 1), C), np.float32)
+            for b in range(B):
+                dense[b, :n_truth[b]] = tfrecord.index_to_one_hot(
+                    truth_index[int(offsets[b]):int(offsets[b + 1])], C)
+            P.write_plots(dict(p, source_length=features.source_length, ground_truth_mel=dense,
+                               ground_truth_mel_length=n_truth), output_dir, hparams,
+                          frames=frames, mel=onehot, **(plot_options or {}))
         index, onehot = _host(index), _host(onehot)
         ids = np.asarray(p["id"]).reshape(-1)
         texts = np.asarray(p["text"], dtype=object).reshape(-1)
         source, source_length = _host(features.source), _host(features.source_length)
-        truth_index, offsets = np.asarray(features.code_index), np.asarray(features.offsets)
         for b, key in enumerate(keys):
             if limit is not None and len(written) >= limit:
                 return written
@@ -97,12 +112,14 @@ def write_code_predictions(pairs: Iterable, output_dir: str, hparams,
 
 
 def predict_codes(model, input_fn, output_dir: str, hparams, checkpoint_path=None,
-                  limit: Optional[int] = None) -> List[str]:
+                  limit: Optional[int] = None, plots: bool = False,
+                  plot_options: Optional[dict] = None) -> List[str]:
     """``model.predict`` over ``input_fn`` beside a second pass over the same batches (the
     ground truth and the unpadded sources), into ``write_code_predictions``."""
     pairs = ((p, features) for p, (features, _) in
              zip(model.predict(input_fn, checkpoint_path=checkpoint_path), input_fn()))
-    return write_code_predictions(pairs, output_dir, hparams, limit=limit)
+    return write_code_predictions(pairs, output_dir, hparams, limit=limit, plots=plots,
+                                  plot_options=plot_options)
 
 
 def main(argv=None) -> int:
@@ -124,6 +141,8 @@ def main(argv=None) -> int:
     ap.add_argument("--batch-size", type=int, default=1, help="utterances per predicted batch")
     ap.add_argument("--seed", type=int, default=1234,
                     help="seed of the prenet dropout masks (apply_dropout_on_inference=True)")
+    ap.add_argument("--plots", action="store_true",
+                    help="also <key>.png: alignments, true and predicted codes as one figure")
     args = ap.parse_args(argv)
     hp = create_hparams(args.hparam_json_file, args.hparams)
     print(hparams_debug_string(hp))
@@ -136,7 +155,8 @@ def main(argv=None) -> int:
     tgt = [os.path.join(args.target_data_root, f"{k}.{hp.target_file_extension}") for k in keys]
     model = tacotron_model_factory(hp, args.checkpoint_dir, None, seed=args.seed)
     done = predict_codes(model, predict_input_fn(hp, src, tgt, args.batch_size), args.output_dir,
-                         hp, checkpoint_path=args.checkpoint, limit=args.limit)
+                         hp, checkpoint_path=args.checkpoint, limit=args.limit,
+                         plots=args.plots)
     print(f"{len(done)} utterances written to {args.output_dir}")
     return 0
 

@@ -17,13 +17,23 @@ utterance that never stops all of them.  The waveforms of one batch are one
 n_fft / 2``: the analysis could not reflect-pad it) is written as a mel file only, with a warning,
 as preprocessing skips what it cannot frame.
 
-Not carried over: the PNG plots and the per-utterance prediction tfrecord of predict_mel.py:63-74.
+Opt-in, the rest of predict_mel.py:63-74:
+
+* ``<key>.png`` (``plots=True``, ``--plots``): the alignments, the decoder self-attention heads,
+  the ground-truth and the predicted mel as one colour figure, composed on the GPU
+  (csrc/figure.hip, ``sat_amd.plots``), each alignment cut at the utterance's own source length and
+  stop step; ``key`` and ``text`` are ``tEXt`` chunks of the file, no text is drawn;
+* ``<key>.tfrecord`` (``records=True``, ``--records``): ``tfrecord.write_prediction_result`` with
+  the fields of utils/tfrecord.py:144-157 -- ``codes`` is the mel as written to the mel file,
+  ``ground_truth_codes`` the target mel up to its own length (no rows where the batch has none).
+  ``tfrecord.parse_prediction_result`` reads it back.
 
 CLI: ``python -m sat_amd.synthesize --source-data-root D --target-data-root D --checkpoint-dir D
 --selected-list-dir D --output-dir D [--checkpoint P] [--selected-list-filename test.csv]
 [--hparams S] [--hparam-json-file F] [--no-wav] [--griffin-lim-iters 60] [--power 1.5]
-[--batch-size 1] [--seed 1234]``.  ``--seed`` seeds the prenet dropout masks of a decode under
-``--hparams apply_dropout_on_inference=True`` (inference.py); the weights come from the checkpoint.
+[--batch-size 1] [--seed 1234] [--plots] [--records]``.  ``--seed`` seeds the prenet dropout masks
+of a decode under ``--hparams apply_dropout_on_inference=True`` (inference.py); the weights come
+from the checkpoint.
 """
 
 from __future__ import annotations
@@ -32,7 +42,7 @@ import argparse
 import os
 import sys
 import warnings
-from typing import Iterable, List
+from typing import Iterable, List, Optional
 
 import numpy as np
 
@@ -61,11 +71,38 @@ def stop_frames(stop, outputs_per_step: int, total_frames: int, min_iters: int =
     return [min(int(t + 1) * int(outputs_per_step), int(total_frames)) for t in first]
 
 
+def _write_records(p: dict, keys, frames, host, output_dir: str) -> None:
+    """``<key>.tfrecord`` of one predicted batch (predict_mel.py:71-74)."""
+    from . import tfrecord
+    B, M = host.shape[0], host.shape[2]
+    ids = np.asarray(p["id"]).reshape(-1)
+    texts = (np.asarray(p["text"], dtype=object).reshape(-1) if p.get("text") is not None
+             else [""] * B)
+    source = _host(p["source"])
+    n_src = (_host(p["source_length"]).reshape(-1) if p.get("source_length") is not None
+             else [source.shape[1]] * B)
+    truth = _host(p["ground_truth_mel"]) if p.get("ground_truth_mel") is not None else None
+    n_truth = (_host(p["ground_truth_mel_length"]).reshape(-1)
+               if truth is not None and p.get("ground_truth_mel_length") is not None else None)
+    for b, key in enumerate(keys):
+        if truth is None:
+            t = np.zeros((0, M), np.float32)
+        else:
+            t = truth[b, :int(n_truth[b])] if n_truth is not None else truth[b]
+        tfrecord.write_prediction_result(int(ids[b]), key, host[b, :frames[b]], t, _key(texts[b]),
+                                         source[b, :int(n_src[b])],
+                                         os.path.join(output_dir, f"{key}.tfrecord"))
+
+
 def write_predictions(predictions: Iterable[dict], output_dir: str, hparams, wav: bool = True,
-                      audio=None, min_iters: int = MIN_ITERS, **gl) -> List[str]:
+                      audio=None, min_iters: int = MIN_ITERS, plots: bool = False,
+                      records: bool = False, plot_options: Optional[dict] = None,
+                      **gl) -> List[str]:
     """Writes the files of every predicted batch (see the module docstring) and returns the keys
     in the order written.  ``gl``: options of ``Audio.inv_melspectrogram_batch`` (``power``,
-    ``n_iter``, ``momentum``, ``seed``); ``audio``: the ``Audio`` to use (built on first need)."""
+    ``n_iter``, ``momentum``, ``seed``); ``audio``: the ``Audio`` to use (built on first need);
+    ``plots`` / ``records``: also ``<key>.png`` / ``<key>.tfrecord``; ``plot_options``: the
+    geometry of ``plots.write_plots`` (``Hp, Wp, margin, cbar, background``)."""
     os.makedirs(output_dir, exist_ok=True)
     r, M = int(hparams.outputs_per_step), int(hparams.num_mels)
     keys_written = []
@@ -84,6 +121,11 @@ def write_predictions(predictions: Iterable[dict], output_dir: str, hparams, wav
             with open(path, "wb") as f:
                 f.write(np.ascontiguousarray(host[b, :frames[b]]).astype("<f4").tobytes())
         keys_written.extend(keys)
+        if plots:
+            from . import plots as P
+            P.write_plots(p, output_dir, hparams, frames=frames, mel=mel, **(plot_options or {}))
+        if records:
+            _write_records(p, keys, frames, host, output_dir)
         if not wav:
             continue
         if audio is None:
@@ -151,6 +193,10 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=1234,
                     help="seed of the prenet dropout masks (apply_dropout_on_inference=True): "
                          "the same seed and key list give the same files")
+    ap.add_argument("--plots", action="store_true",
+                    help="also <key>.png: alignments and mels as one colour figure")
+    ap.add_argument("--records", action="store_true",
+                    help="also <key>.tfrecord: the prediction record (codes = the predicted mel)")
     args = ap.parse_args(argv)
     hp = create_hparams(args.hparam_json_file, args.hparams)
     print(hparams_debug_string(hp))
@@ -163,6 +209,7 @@ def main(argv=None) -> int:
     preds = model.predict(predict_input_fn(hp, src, tgt, args.batch_size),
                           checkpoint_path=args.checkpoint)
     done = write_predictions(preds, args.output_dir, hp, wav=not args.no_wav,
+                             plots=args.plots, records=args.records,
                              n_iter=args.griffin_lim_iters, power=args.power)
     print(f"{len(done)} utterances written to {args.output_dir}")
     return 0
