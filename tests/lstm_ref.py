@@ -1,7 +1,8 @@
-"""Plain-torch restatement of the zoneout LSTM kernels (csrc/lstm.hip, csrc/encoder_lstm.hip) in
-the kernels' own layout, dtype-generic (float64 for the reference, float32 to measure what the
-number format alone costs).  Shared by test_lstm_ref_cpu.py (which ties it to the oracle),
-test_lstm_gpu.py and test_encoder_lstm_gpu.py.
+"""Plain-torch restatement of the zoneout LSTM kernels (csrc/lstm.hip, csrc/encoder_lstm.hip,
+csrc/decoder_lstm_persistent.hip) in the kernels' own layout, dtype-generic (float64 for the
+reference, float32 to measure what the number format alone costs).  Shared by
+test_lstm_ref_cpu.py (which ties it to the oracle), test_lstm_gpu.py, test_encoder_lstm_gpu.py
+and test_decoder_lstms_gpu.py.
 
 Layout: weights [K][U][4], gates / gate gradients [B][U][4], gate order i, j, f, o, forget
 bias 1.  Zoneout: masks (1 = take the new value) or, with ``mc is None``, the eval blend
@@ -124,3 +125,36 @@ def bilstm(X_fw, X_bw, W_fw, W_bw, lengths, masks, zc, zh, init=None):
         HSs.append(torch.stack(hs))
         Gs.append(torch.stack(g))
     return torch.cat(Hs, dim=-1), tuple(CSs), tuple(HSs), tuple(Gs)
+
+
+def decoder_stack(X1, W1r, W2, b2, init, masks, zc, zh, X2=None):
+    """The decoder's two stacked ZoneoutLSTM layers over all T steps, in SatDecLstmFwd's layout.
+
+    ``X1`` [T][B][4U] (LSTM1's hoisted input projection + bias, gate-interleaved), ``W1r``
+    [U][U][4] (LSTM1's recurrent rows), ``W2`` [2U][U][4] (LSTM2's input rows, then its recurrent
+    rows), ``b2`` [U][4] (or [4U]), ``init`` = (c1, h1, c2, h2) each [B][U], ``masks`` None (eval
+    blend) or (m1c, m1h, m2c, m2h) each [T][B][U], ``X2`` optional [T][B][4U] added to LSTM2's
+    pre-activations (pass zeros: it exists so that autograd yields LSTM2's gate gradients).
+
+    Per step LSTM1 takes X1[t] and rows h1_{t-1}; LSTM2 takes b2 (+ X2[t]) and rows
+    [h1'_t | h2_{t-1}] -- LSTM1's RAW output, not its zoned-out state.
+
+    Returns H1RAW [T][B][U], C1S, H1S [T+1][B][U] (row 0 = the initial state), G1 [T][B][4U],
+    then H2RAW, C2S, H2S, G2 likewise.  Differentiable."""
+    T, B, G4 = X1.shape
+    U = G4 // 4
+    W1r = W1r.reshape(U, U, 4)
+    W2 = W2.reshape(2 * U, U, 4)
+    b2 = b2.reshape(U, 4)
+    c1, h1, c2, h2 = init
+    raw1, cs1, hs1, g1 = [], [c1], [h1], []
+    raw2, cs2, hs2, g2 = [], [c2], [h2], []
+    for t in range(T):
+        m = (None,) * 4 if masks is None else tuple(mk[t] for mk in masks)
+        r1, c1, h1, gt1, _ = step(X1[t].reshape(B, U, 4), h1, W1r, c1, h1, m[0], m[1], zc, zh)
+        xb2 = b2 if X2 is None else b2 + X2[t].reshape(B, U, 4)
+        r2, c2, h2, gt2, _ = step(xb2, torch.cat([r1, h2], dim=-1), W2, c2, h2, m[2], m[3], zc, zh)
+        raw1.append(r1), cs1.append(c1), hs1.append(h1), g1.append(gt1.reshape(B, G4))
+        raw2.append(r2), cs2.append(c2), hs2.append(h2), g2.append(gt2.reshape(B, G4))
+    st = torch.stack
+    return st(raw1), st(cs1), st(hs1), st(g1), st(raw2), st(cs2), st(hs2), st(g2)

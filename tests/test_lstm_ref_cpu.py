@@ -195,3 +195,91 @@ def test_bilstm_gate_gradients_are_step_bwd():
             for b_, L in enumerate(lengths.tolist()):
                 if n >= L:
                     assert torch.equal(ref[b_], torch.zeros(U, 4, dtype=F64))
+
+
+def _stack_case(g, T, B, U, masked):
+    """Random decoder-stack operands in float64: hoisted X1, the three weights, a non-zero
+    initial state, masks (or None) and a head gradient."""
+    X1 = _rand(g, T, B, 4 * U)
+    W1r, W2 = _rand(g, U, U, 4, scale=0.5), _rand(g, 2 * U, U, 4, scale=0.4)
+    b2 = _rand(g, U, 4, scale=0.3)
+    init = tuple(_rand(g, B, U, scale=0.5) for _ in range(4))
+    masks = None
+    if masked:
+        masks = tuple((torch.rand(T, B, U, generator=g) < 0.6).to(F64) for _ in range(4))
+    return X1, W1r, W2, b2, init, masks, _rand(g, T, B, U)
+
+
+@pytest.mark.parametrize("masked", [True, False])
+def test_decoder_stack_matches_oracle(masked):
+    """lstm_ref.decoder_stack == a chain of oracle.zoneout_lstm_step calls wired as the oracle's
+    decoder_loop wires lstm1 into lstm2 (lstm2's input is lstm1's RAW output), float64 to 1e-12:
+    masks and the eval blend, a non-zero initial state, zc != zh.  State row t + 1 is the state
+    after step t, row 0 the state given; the gates are the oracle cell's activated [i j f o]."""
+    from oracle import sat_oracle as O
+    g = torch.Generator().manual_seed(31 + masked)
+    T, B, U, I = 6, 3, 5, 7
+    zc, zh = 0.1, 0.15
+    x = _rand(g, T, B, I)
+    w1, b1 = _rand(g, I + U, 4 * U, scale=0.3), _rand(g, 4 * U, scale=0.3)
+    w2, b2 = _rand(g, 2 * U, 4 * U, scale=0.3), _rand(g, 4 * U, scale=0.3)
+    init = tuple(_rand(g, B, U, scale=0.5) for _ in range(4))
+    masks = None
+    if masked:
+        masks = tuple((torch.rand(T, B, U, generator=g) < 0.6).to(F64) for _ in range(4))
+    W1i, b1i = _internal(w1, b1)
+    W2i, b2i = _internal(w2, b2)
+    X1 = ((x.reshape(T * B, I) @ W1i[:I].reshape(I, -1)).view(T, B, U, 4) + b1i).reshape(T, B, 4 * U)
+    H1RAW, C1S, H1S, G1, H2RAW, C2S, H2S, G2 = R.decoder_stack(X1, W1i[I:], W2i, b2i, init, masks,
+                                                               zc, zh)
+    assert H1RAW.shape == H2RAW.shape == (T, B, U) and G1.shape == G2.shape == (T, B, 4 * U)
+    assert C1S.shape == H1S.shape == C2S.shape == H2S.shape == (T + 1, B, U)
+    for got, ref in zip((C1S[0], H1S[0], C2S[0], H2S[0]), init):
+        assert torch.equal(got, ref)
+    cc1, hh1, cc2, hh2 = init
+    for t in range(T):
+        m = (None,) * 4 if masks is None else tuple(mk[t] for mk in masks)
+        z1 = torch.cat([x[t], hh1], dim=-1) @ w1 + b1
+        h1_out, cc1, hh1 = O.zoneout_lstm_step(x[t], cc1, hh1, w1, b1, zc, zh, m[0], m[1])
+        z2 = torch.cat([h1_out, hh2], dim=-1) @ w2 + b2
+        h2_out, cc2, hh2 = O.zoneout_lstm_step(h1_out, cc2, hh2, w2, b2, zc, zh, m[2], m[3])
+        for got, ref in ((H1RAW[t], h1_out), (C1S[t + 1], cc1), (H1S[t + 1], hh1),
+                         (H2RAW[t], h2_out), (C2S[t + 1], cc2), (H2S[t + 1], hh2)):
+            assert float((got - ref).abs().max()) <= 1e-12
+        for got, z in ((G1[t], z1), (G2[t], z2)):
+            i, j, f, o = torch.chunk(z, 4, dim=-1)
+            ref_g = torch.cat([torch.sigmoid(i), torch.tanh(j), torch.sigmoid(f + 1.0),
+                               torch.sigmoid(o)], -1)
+            assert float((_gates_tf(got) - ref_g).abs().max()) <= 1e-12
+    # X2 = 0 changes nothing
+    again = R.decoder_stack(X1, W1i[I:], W2i, b2i, init, masks, zc, zh,
+                            X2=torch.zeros(T, B, 4 * U, dtype=F64))
+    assert torch.equal(again[4], H2RAW) and torch.equal(again[7], G2)
+
+
+@pytest.mark.parametrize("masked", [True, False])
+def test_decoder_stack_gate_gradients_are_step_bwd(masked):
+    """What the GPU test calls DG1 / DG2: autograd of sum(H2RAW . DH2) w.r.t. X1 and X2 equals a
+    reverse loop of lstm_ref.step_bwd over both layers (1e-10) -- LSTM2 with dy = DH2[t] and its
+    recurrent rows W2[U:], LSTM1 with dy = dgates2_t . W2[:U] (the gradient of its raw output
+    through LSTM2's input rows) and its own recurrent product."""
+    g = torch.Generator().manual_seed(41 + masked)
+    T, B, U = 6, 3, 4
+    zc, zh = 0.1, 0.15
+    X1, W1r, W2, b2, init, masks, DH2 = _stack_case(g, T, B, U, masked)
+    X1 = X1.requires_grad_(True)
+    X2 = torch.zeros(T, B, 4 * U, dtype=F64, requires_grad=True)
+    H1RAW, C1S, H1S, G1, H2RAW, C2S, H2S, G2 = R.decoder_stack(X1, W1r, W2, b2, init, masks, zc,
+                                                               zh, X2=X2)
+    (H2RAW * DH2).sum().backward()
+    dg1 = dg2 = dh1 = dc1 = dh2 = dc2 = None
+    for t in reversed(range(T)):
+        m = (None,) * 4 if masks is None else tuple(mk[t] for mk in masks)
+        dg2, dh2, dc2 = R.step_bwd(W2, U, G2[t].detach().view(B, U, 4), C2S[t].detach(), dg2, None,
+                                   DH2[t], None, dh2, dc2, m[2], m[3], zc, zh)
+        dy1 = torch.einsum("bvg,uvg->bu", dg2, W2[:U])
+        dg1, dh1, dc1 = R.step_bwd(W1r, 0, G1[t].detach().view(B, U, 4), C1S[t].detach(), dg1, None,
+                                   dy1, None, dh1, dc1, m[0], m[1], zc, zh)
+        assert float((dg2.reshape(B, -1) - X2.grad[t]).abs().max()) <= 1e-10
+        assert float((dg1.reshape(B, -1) - X1.grad[t]).abs().max()) <= 1e-10
+        assert float(dg1.abs().max()) > 0.0 and float(dg2.abs().max()) > 0.0
