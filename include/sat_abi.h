@@ -407,6 +407,38 @@ int sat_decode_persistent_spk(const SatDecodePersistent* a, const SatDecodeSpeak
 int sat_decode_persistent_spk_dropout(const SatDecodePersistent* a, const SatDecodeSpeaker* s,
                                       const uint64_t* seed_ptr, uint64_t stream1, float keep,
                                       void* stream);
+/* The same decode for any output width (num_mels x outputs_per_step; the VQ-code corpora have
+ * num_mels = num_codes, r = 1: hparams.py codes preset, codes/dataset.py).  Only two things in a
+ * step depend on the output projection -- the stop column and the fed frame, and the caller folds
+ * the fed frame into the first prenet layer (Wzp = W_out[:, -feed:] W_p0, bzp = b_out[-feed:] W_p0
+ * + b_p0, feed = num_mels: with r = 1 the whole projection).  So the step forms the stop value
+ * alone, stop = z . w_stop + b_stop, and stores the head output z of every step; the caller
+ * projects the history once after the launch (mel[:steps] = ZH[:steps] W_out + b_out, one GEMM).
+ *   ZH[t][b][0:256]  the z row of step t (16-byte aligned),  STOP[t][b]  its stop logit;
+ *   w_stop [256], b_stop [1]  the stop projection (stop_token_projection kernel / bias).
+ * Rows after the first finished step are left unwritten, as those of MS are.  Wms, bms
+ * and MS of SatDecodePersistent are unused here and may be null; every other field, the stop
+ * test, state, err and the scratch of sat_decode_persistent_scratch_bytes() are as above.
+ * _hist / _hist_dropout / _hist_spk / _hist_spk_dropout mirror the four entries above argument
+ * for argument.  Separate kernel instantiations in a module of their own: the four entries above
+ * are unaffected. */
+typedef struct SatDecodeHistory {
+  float* ZH;              /* [T][B][256] */
+  float* STOP;            /* [T][B] */
+  const float* w_stop;    /* [256] */
+  const float* b_stop;    /* [1] */
+} SatDecodeHistory;
+int sat_decode_persistent_hist(const SatDecodePersistent* a, const SatDecodeHistory* h,
+                               void* stream);
+int sat_decode_persistent_hist_dropout(const SatDecodePersistent* a, const SatDecodeHistory* h,
+                                       const uint64_t* seed_ptr, uint64_t stream0,
+                                       uint64_t stream1, float keep, void* stream);
+int sat_decode_persistent_hist_spk(const SatDecodePersistent* a, const SatDecodeSpeaker* s,
+                                   const SatDecodeHistory* h, void* stream);
+int sat_decode_persistent_hist_spk_dropout(const SatDecodePersistent* a,
+                                           const SatDecodeSpeaker* s, const SatDecodeHistory* h,
+                                           const uint64_t* seed_ptr, uint64_t stream1, float keep,
+                                           void* stream);
 
 /* ---------------------------------------------------------------- (Zoneout)LSTM step
  * One time step of TF LSTMCell wrapped in ext tacotron2 ZoneoutLSTMCell,

@@ -165,6 +165,8 @@ SatDecodePersistent = _struct("SatDecodePersistent", """
 
 SatDecodeSpeaker = _struct("SatDecodeSpeaker", "ptr:spk0 ptr:Wd ptr:bd")
 
+SatDecodeHistory = _struct("SatDecodeHistory", "ptr:ZH ptr:STOP ptr:w_stop ptr:b_stop")
+
 
 class SatDecoderLoopFwd(ctypes.Structure):   # mirrors include/sat_abi.h
     _fields_ = [("attn", SatDecAttnFwd), ("lstm", SatDecLstmFwd), ("W1x", _P), ("b1", _P),
@@ -259,6 +261,18 @@ SIGNATURES = {
                                   ctypes.POINTER(SatDecodeSpeaker), _P],
     "sat_decode_persistent_spk_dropout": [ctypes.POINTER(SatDecodePersistent),
                                           ctypes.POINTER(SatDecodeSpeaker), _P, _U64, _F, _P],
+    "sat_decode_persistent_hist": [ctypes.POINTER(SatDecodePersistent),
+                                   ctypes.POINTER(SatDecodeHistory), _P],
+    "sat_decode_persistent_hist_dropout": [ctypes.POINTER(SatDecodePersistent),
+                                           ctypes.POINTER(SatDecodeHistory), _P, _U64, _U64, _F,
+                                           _P],
+    "sat_decode_persistent_hist_spk": [ctypes.POINTER(SatDecodePersistent),
+                                       ctypes.POINTER(SatDecodeSpeaker),
+                                       ctypes.POINTER(SatDecodeHistory), _P],
+    "sat_decode_persistent_hist_spk_dropout": [ctypes.POINTER(SatDecodePersistent),
+                                               ctypes.POINTER(SatDecodeSpeaker),
+                                               ctypes.POINTER(SatDecodeHistory), _P, _U64, _F,
+                                               _P],
     "sat_zlstm_step_fwd": [ctypes.POINTER(SatLstmFwd), _P],
     "sat_zlstm_step_bwd": [ctypes.POINTER(SatLstmBwd), _P],
     "sat_attn_param_grad_rows": [_I32, _I32],

@@ -21,6 +21,8 @@
 // Per step t (group b, workgroup w owns LSTM units 8w..8w+7 and 8 / 4 / 32 dense columns):
 //   P1  z_{t-1} -> mel|stop of step t-1 (outputs, stop granule to every group) and the first
 //       prenet layer of step t (the fed frame is folded in: Wzp = W_out[:, fed] W_p0)
+//       (history kernels, kHist: only the stop value is formed; the z_{t-1} row goes to ZH and
+//       the caller projects the whole history once after the launch -- any num_mels and r)
 //   P1b (multi-speaker kernels only, kSpk: one more all-gather) the second dense of the
 //       MultiSpeakerPreNet: P1 publishes d0 = relu(dense0) + speaker row, P1b its dense + ReLU
 //   P2  prenet layer 2                         P3  attention RNN (ZoneoutLSTM 256)
@@ -179,10 +181,24 @@ struct SpkArgs<true> {
   SatDecodeSpeaker s;
 };
 
-template <bool kDrop, bool kSpk>
+// The history variant (kHist = true: sat_decode_persistent_hist*).  Only two things in a step
+// depend on the output projection: the stop column and the fed frame, and the fed frame is folded
+// into Wzp by the caller.  So P1 forms the stop value alone (workgroup 0 of the group, wave 0) and
+// stores the gathered z_{t-1} row to ZH[t-1][b]; Wms / bms / MS of SatDecodePersistent are
+// unused and the output width (num_mels x r) is no property of the kernel.  kHist = false
+// carries an empty struct: the mel-row kernels hold no trace of it.
+template <bool kHist>
+struct HistArgs {};
+template <>
+struct HistArgs<true> {
+  SatDecodeHistory h;
+};
+
+template <bool kDrop, bool kSpk, bool kHist>
 __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersistent p,
                                                                 DropArgs<kDrop> args,
-                                                                SpkArgs<kSpk> spk) {
+                                                                SpkArgs<kSpk> spk,
+                                                                HistArgs<kHist> hist) {
   const int g = blockIdx.x % kG, w = blockIdx.x / kG;
   if (g >= p.B) return;   // no utterance: no partner outside this group
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -255,7 +271,8 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
   // dense columns: prenet-1 col 8w+wave from z, mel|stop col w+32 wave, prenet-2 col 4w+wave,
   // query col 8w+wave, q|k|u cols 32w + 4 wave + j
   const int cpre = 8 * w + wave, cmel = w + 32 * wave, cp1 = 4 * w + wave, cq = 8 * w + wave;
-  const bool has_mel = wave < 6 && cmel <= kMR;
+  // (kHist: no mel columns and no wms -- the stop column is read where it is used, by one wave)
+  const bool has_mel = !kHist && wave < 6 && cmel <= kMR;
   float wzp[4], wms[4], wp1[4], wq[4], wk[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -317,8 +334,10 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
     cbzp[tid] = p.bzp[8 * w + tid];
     cbp0[tid] = p.bp0[8 * w + tid];
     cbz[tid] = p.bz[8 * w + tid];
-    const int cm = w + 32 * tid;
-    cbms[tid] = (tid < 6 && cm <= kMR) ? p.bms[cm] : 0.f;
+    if constexpr (!kHist) {
+      const int cm = w + 32 * tid;
+      cbms[tid] = (tid < 6 && cm <= kMR) ? p.bms[cm] : 0.f;
+    }
     if (tid < 4) cbp1[tid] = p.bp1[4 * w + tid];
     if constexpr (kSpk) {
       cspk[tid] = spk.s.spk0[(size_t)g * kP0 + 8 * w + tid];
@@ -379,7 +398,24 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
       gather<1>(R, (oZ + sp * kSD) / 4, kSD / 4, reinterpret_cast<float4*>(xz), bp, p.err);
       lds_barrier();
       TP(1)
-      if (wave < 6) {
+      if constexpr (kHist) {
+        // the z history: row t-1 is stored by workgroup (t-1) % 32 of the group, one float4 per
+        // thread of its first wave (plain stores: read after the launch only)
+        if (((t - 1) & (kW - 1)) == w && tid < kSD / 4)
+          reinterpret_cast<float4*>(hist.h.ZH + ((size_t)(t - 1) * p.B + g) * kSD)[tid] =
+              reinterpret_cast<const float4*>(xz)[tid];
+        if (w == 0 && wave == 0) {   // the stop value of step t-1 (w_stop: 1 KB, cache resident)
+          float a = 0.f;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) a = fmaf(xz[lane + 64 * i], hist.h.w_stop[lane + 64 * i], a);
+          a = wave_sum_dpp(a);
+          if (lane == 0) {
+            const float v = a + hist.h.b_stop[0];
+            hist.h.STOP[(size_t)(t - 1) * p.B + g] = v;
+            stg(RS, sp * 8 + g, v, (unsigned)t);   // {stop_{t-1}, t} to every group
+          }
+        }
+      } else if (wave < 6) {
         float a = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) a = fmaf(xz[lane + 64 * i], wms[i], a);
@@ -809,30 +845,32 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
 
 using namespace sat;
 
-// The entries live in two modules built from this one source: the single-speaker pair here, the
+// The entries live in three modules built from this one source: the single-speaker pair here, the
 // multi-speaker pair in decode_persistent_spk.hip (which defines SAT_DP_SPK and includes this
-// file).  One module holding all four kernels compiles the single-speaker pair to another
-// instruction stream than the module without the multi-speaker pair does; apart, adding the
-// kSpk kernels leaves the existing two exactly as they were (`make asm`).
-#ifndef SAT_DP_SPK
+// file), the four history entries in decode_persistent_hist.hip (SAT_DP_HIST).  One module holding
+// all the kernels compiles the single-speaker pair to another instruction stream than the module
+// without the others does; apart, adding kernels leaves the existing ones exactly as they were
+// (`make asm`).
+#if !defined(SAT_DP_SPK) && !defined(SAT_DP_HIST)
 extern "C" int64_t sat_decode_persistent_scratch_bytes(void) {
   return (kZeroDwords + kCacheFloats + kD0Dwords) * 4;
 }
 #endif
 
-// Argument checks, co-residency test, scratch clear and launch shared by the four entries.
-template <bool kDrop, bool kSpk>
+// Argument checks, co-residency test, scratch clear and launch shared by every entry.
+template <bool kDrop, bool kSpk, bool kHist>
 static int launch_decode(const SatDecodePersistent* a, const DropArgs<kDrop>& args,
-                         const SpkArgs<kSpk>& spk, void* stream) {
+                         const SpkArgs<kSpk>& spk, const HistArgs<kHist>& hist, void* stream) {
   SAT_CHECK_ARG(a && a->B >= 1 && a->B <= kG && a->N >= 1 && a->N <= kNM && a->T >= 1 &&
                     a->T <= kW * kRM,
                 "sat_decode_persistent: B <= 8, N <= 256, T <= 512 (got B=%d N=%d T=%d)",
                 a ? a->B : 0, a ? a->N : 0, a ? a->T : 0);
+  // the mel-row entries write MS through Wms / bms; the history entries leave the three unused
   SAT_CHECK_ARG(a->lengths && a->K1 && a->V1 && a->K2 && a->V2 && a->Wzp && a->bzp && a->bp0 &&
                     a->Wp1 && a->bp1 && a->W0 && a->b0 && a->Wq && a->b1 && a->v1 && a->convW &&
                     a->convb && a->locW && a->v2 && a->W1 && a->bl1 && a->W2 && a->bl2 &&
-                    a->Wqku && a->bqku && a->bz && a->Wms && a->bms && a->MS && a->AL1 &&
-                    a->S2 && a->state && a->scratch && a->err,
+                    a->Wqku && a->bqku && a->bz && (kHist || (a->Wms && a->bms && a->MS)) &&
+                    a->AL1 && a->S2 && a->state && a->scratch && a->err,
                 "sat_decode_persistent: null pointer");
   SAT_CHECK_ARG(a->scratch_bytes >= sat_decode_persistent_scratch_bytes(),
                 "sat_decode_persistent: scratch too small");
@@ -842,8 +880,8 @@ static int launch_decode(const SatDecodePersistent* a, const DropArgs<kDrop>& ar
   int dev = 0, cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_persistent_kernel<kDrop, kSpk>,
-                                                   kTh, 0) != hipSuccess) {
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &per_cu, decode_persistent_kernel<kDrop, kSpk, kHist>, kTh, 0) != hipSuccess) {
     set_error("sat_decode_persistent: device query failed");
     return SAT_ERR_HIP;
   }
@@ -859,8 +897,8 @@ static int launch_decode(const SatDecodePersistent* a, const DropArgs<kDrop>& ar
     set_error("sat_decode_persistent: scratch clear failed");
     return SAT_ERR_HIP;
   }
-  hipLaunchKernelGGL((decode_persistent_kernel<kDrop, kSpk>), dim3(kG * kW), dim3(kTh), 0, s, *a,
-                     args, spk);
+  hipLaunchKernelGGL((decode_persistent_kernel<kDrop, kSpk, kHist>), dim3(kG * kW), dim3(kTh), 0,
+                     s, *a, args, spk, hist);
   SAT_LAUNCH_CHECK("sat_decode_persistent");
   return SAT_OK;
 }
@@ -874,9 +912,10 @@ static void drop_args(const uint64_t* seed_ptr, uint64_t stream0, uint64_t strea
   args->on = (float)(1.0 / (double)keep);
 }
 
-#ifndef SAT_DP_SPK
+#if !defined(SAT_DP_SPK) && !defined(SAT_DP_HIST)
 extern "C" int sat_decode_persistent(const SatDecodePersistent* a, void* stream) {
-  return launch_decode<false, false>(a, DropArgs<false>{}, SpkArgs<false>{}, stream);
+  return launch_decode<false, false, false>(a, DropArgs<false>{}, SpkArgs<false>{},
+                                            HistArgs<false>{}, stream);
 }
 
 extern "C" int sat_decode_persistent_dropout(const SatDecodePersistent* a, const uint64_t* seed_ptr,
@@ -887,16 +926,16 @@ extern "C" int sat_decode_persistent_dropout(const SatDecodePersistent* a, const
                 (double)keep);
   DropArgs<true> args;
   drop_args(seed_ptr, stream0, stream1, keep, &args);
-  return launch_decode<true, false>(a, args, SpkArgs<false>{}, stream);
+  return launch_decode<true, false, false>(a, args, SpkArgs<false>{}, HistArgs<false>{}, stream);
 }
-#else
+#elif defined(SAT_DP_SPK)
 
 extern "C" int sat_decode_persistent_spk(const SatDecodePersistent* a, const SatDecodeSpeaker* sp,
                                          void* stream) {
   SAT_CHECK_ARG(a && sp && sp->spk0 && sp->Wd && sp->bd, "sat_decode_persistent_spk: null pointer");
   SpkArgs<true> spk;
   spk.s = *sp;
-  return launch_decode<false, true>(a, DropArgs<false>{}, spk, stream);
+  return launch_decode<false, true, false>(a, DropArgs<false>{}, spk, HistArgs<false>{}, stream);
 }
 
 extern "C" int sat_decode_persistent_spk_dropout(const SatDecodePersistent* a,
@@ -911,6 +950,66 @@ extern "C" int sat_decode_persistent_spk_dropout(const SatDecodePersistent* a,
   drop_args(seed_ptr, 0, stream1, keep, &args);   // stream0: layer 0 never drops here
   SpkArgs<true> spk;
   spk.s = *sp;
-  return launch_decode<true, true>(a, args, spk, stream);
+  return launch_decode<true, true, false>(a, args, spk, HistArgs<false>{}, stream);
 }
+#else
+
+// ---- the history entries (kHist = true): the shape check first, as in every entry, then the
+// history struct's own pointers; nothing is launched on a bad argument
+#define SAT_DP_HIST_CHECK(name)                                                                  \
+  SAT_CHECK_ARG(a && a->B >= 1 && a->B <= kG && a->N >= 1 && a->N <= kNM && a->T >= 1 &&        \
+                    a->T <= kW * kRM,                                                            \
+                name ": B <= 8, N <= 256, T <= 512 (got B=%d N=%d T=%d)", a ? a->B : 0,          \
+                a ? a->N : 0, a ? a->T : 0);                                                     \
+  SAT_CHECK_ARG(h && h->ZH && h->STOP && h->w_stop && h->b_stop, name ": null pointer");         \
+  SAT_CHECK_ARG(aligned16(h->ZH), name ": ZH must be 16-byte aligned");                          \
+  HistArgs<true> hist;                                                                           \
+  hist.h = *h
+
+extern "C" int sat_decode_persistent_hist(const SatDecodePersistent* a, const SatDecodeHistory* h,
+                                          void* stream) {
+  SAT_DP_HIST_CHECK("sat_decode_persistent_hist");
+  return launch_decode<false, false, true>(a, DropArgs<false>{}, SpkArgs<false>{}, hist, stream);
+}
+
+extern "C" int sat_decode_persistent_hist_dropout(const SatDecodePersistent* a,
+                                                  const SatDecodeHistory* h,
+                                                  const uint64_t* seed_ptr, uint64_t stream0,
+                                                  uint64_t stream1, float keep, void* stream) {
+  SAT_DP_HIST_CHECK("sat_decode_persistent_hist_dropout");
+  SAT_CHECK_ARG(seed_ptr, "sat_decode_persistent_hist_dropout: null pointer");
+  SAT_CHECK_ARG(keep > 0.f, "sat_decode_persistent_hist_dropout: keep must be > 0 (got %g)",
+                (double)keep);
+  DropArgs<true> args;
+  drop_args(seed_ptr, stream0, stream1, keep, &args);
+  return launch_decode<true, false, true>(a, args, SpkArgs<false>{}, hist, stream);
+}
+
+extern "C" int sat_decode_persistent_hist_spk(const SatDecodePersistent* a,
+                                              const SatDecodeSpeaker* sp,
+                                              const SatDecodeHistory* h, void* stream) {
+  SAT_DP_HIST_CHECK("sat_decode_persistent_hist_spk");
+  SAT_CHECK_ARG(sp && sp->spk0 && sp->Wd && sp->bd, "sat_decode_persistent_hist_spk: null pointer");
+  SpkArgs<true> spk;
+  spk.s = *sp;
+  return launch_decode<false, true, true>(a, DropArgs<false>{}, spk, hist, stream);
+}
+
+extern "C" int sat_decode_persistent_hist_spk_dropout(const SatDecodePersistent* a,
+                                                      const SatDecodeSpeaker* sp,
+                                                      const SatDecodeHistory* h,
+                                                      const uint64_t* seed_ptr, uint64_t stream1,
+                                                      float keep, void* stream) {
+  SAT_DP_HIST_CHECK("sat_decode_persistent_hist_spk_dropout");
+  SAT_CHECK_ARG(sp && sp->spk0 && sp->Wd && sp->bd && seed_ptr,
+                "sat_decode_persistent_hist_spk_dropout: null pointer");
+  SAT_CHECK_ARG(keep > 0.f, "sat_decode_persistent_hist_spk_dropout: keep must be > 0 (got %g)",
+                (double)keep);
+  DropArgs<true> args;
+  drop_args(seed_ptr, 0, stream1, keep, &args);   // stream0: layer 0 never drops here
+  SpkArgs<true> spk;
+  spk.s = *sp;
+  return launch_decode<true, true, true>(a, args, spk, hist, stream);
+}
+#undef SAT_DP_HIST_CHECK
 #endif

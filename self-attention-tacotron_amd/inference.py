@@ -140,8 +140,12 @@ class FreeRunningDecoder:
     it whenever the shape allows (mel feedback, no forced alignments, the LJSpeech / VCTK decoder
     dimensions -- single speaker, or the speaker embedding fed to the prenet only
     (``speaker_embedd_to_prenet``; not ``speaker_embedd_to_decoder``) --, no transition agent or
-    cumulative weights, B <= 8, N <= 256, T' <= 512), True requires it, False keeps the per-step
-    launches.
+    cumulative weights, one fed frame, B <= 8, N <= 256, T' <= 512), True requires it, False
+    keeps the per-step launches.  80 mels x r = 2 runs the mel-row entries (an 80-mel model
+    with another r stays on the per-step launches), any other ``num_mels`` with any
+    ``outputs_per_step`` (the codes corpora: ``num_mels = num_codes``, r = 1) the history
+    entries (``sat_decode_persistent_hist*``), which store the head output of every step and
+    leave the projection to one product after the launch.
     ``seed``: the seed of the prenet masks under ``apply_dropout_on_inference`` -- an int (a
     device word of its own is made) or a one-element int64 device tensor the caller shares
     between decoders; every ``run()`` advances it by one.  Unused with the switch off.  With the
@@ -221,12 +225,20 @@ class FreeRunningDecoder:
     # ------------------------------------------------------------------ one-launch decode
     def _why_not(self, B: int, N: int, Tm: int) -> str:
         d, hp = self.d, self.hp
-        dims = dict(dec_prenet=(256, 128), feed=80, att_rnn=256, m1=256, m2=32, d1=224, d2=32,
-                    loc_k=10, loc_f=5, dec=256, dsa=256, dec_heads=2, dec_hops=1, num_mels=80, r=2,
+        # the decoder widths the kernels are compiled for.  The output shape is not among them:
+        # num_mels = 80, r = 2 (LJSpeech / VCTK) takes the mel-row entries, every other
+        # num_mels with any r -- the codes corpora: num_mels = num_codes, r = 1 -- the history entries,
+        # which keep z and leave the projection to one product after the launch (_uses_history)
+        dims = dict(dec_prenet=(256, 128), att_rnn=256, m1=256, m2=32, d1=224, d2=32,
+                    loc_k=10, loc_f=5, dec=256, dsa=256, dec_heads=2, dec_hops=1,
                     att1="forward", att2="additive")
         for k, v in dims.items():
             if getattr(d, k) != v:
                 return f"{k}={getattr(d, k)!r}, needs {v!r}"
+        if d.num_mels == 80 and d.r != 2:
+            # the 80-mel models belong to the mel-row kernels, compiled for r = 2: another r of
+            # such a model stays on the per-step path with the reason it always had
+            return f"r={d.r!r}, needs 2"
         if d.spk_to_decoder:
             # sat_decode_persistent has no per-utterance input rows for the speaker terms
             return "speaker_embedd_to_decoder is on the per-step path only"
@@ -247,6 +259,12 @@ class FreeRunningDecoder:
     def _persistent_ok(self, B: int, N: int, Tm: int) -> bool:
         return self._why_not(B, N, Tm) == ""
 
+    def _uses_history(self) -> bool:
+        """Which one-launch entries an eligible model takes: the mel-row kernels are compiled
+        for 80 mels x r = 2 (and _why_not admits no other r at 80 mels); any other width runs
+        the history kernels."""
+        return self.d.num_mels != 80
+
     def _build_persistent(self, pl: _Plan) -> None:
         """Packed weights of sat_decode_persistent (refilled from the parameters every run) and
         its scratch; see include/sat_abi.h SatDecodePersistent."""
@@ -259,6 +277,21 @@ class FreeRunningDecoder:
         pl.scratch = torch.empty(K.decode_persistent_scratch_bytes(), dtype=torch.uint8,
                                  device=dev)
         pl.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        # the history entries: the head output z and the stop logit of every step (static, like
+        # every buffer of the plan; rows past the last step of a run are never read)
+        pl.ZH = pl.STOPH = None
+        if self._uses_history():
+            pl.ZH = torch.zeros(pl.Tm, pl.B, 256, **f32)
+            pl.STOPH = torch.zeros(pl.Tm, pl.B, **f32)
+
+    def _project_history(self, pl: _Plan, steps: int) -> None:
+        """The history entries' output projection, off the serial path: MS[:steps] = ZH[:steps]
+        [W_out | w_stop | 0] + [b_out | b_stop | 0] as ONE product over all steps and utterances
+        (the packed weights' columns are padded to a multiple of 4 here, whatever num_mels is).
+        The stop column is then overwritten with the logits the kernel formed and tested."""
+        rows = steps * pl.B
+        K.gemm(pl.ZH[:steps].view(rows, 256), pl.Wms, pl.MS[:steps].view(rows, -1), bias=pl.bms)
+        pl.STOP[:steps, :, 0].copy_(pl.STOPH[:steps])
 
     def _pack_persistent(self, pl: _Plan) -> None:
         """Fold the fed frame into the first prenet layer and the value / output projection /
@@ -298,19 +331,32 @@ class FreeRunningDecoder:
         self._pack_persistent(pl)
         pk = pl.pk
         p0 = "decoder/prenet0"
+        # the history entries (any output width) take the same arguments behind their struct
+        # and no mel-row fields; the 80 x 2 models keep the mel-row entries
+        hist = pl.ZH is not None
+        pre = ()
+        if hist:
+            st = "decoder/stop_token_projection"
+            pre = ((pl.ZH, pl.STOPH, P[f"{st}/kernel"], P[f"{st}/bias"]),)
         if d.multi_speaker:
             # layer 0 = MultiSpeakerPreNet: pl.sp is the softsign row _prepare formed for both
             # paths; under the dropout switch only layer 1 drops (prenet_drops)
             p0, ms = "decoder/prenet0/dense0", "decoder/prenet0/dense"
             spk = (pl.sp, P[f"{ms}/kernel"], P[f"{ms}/bias"])
             if self.drop:
-                launch = functools.partial(K.decode_persistent_spk_dropout, *spk, self.seed,
-                                           DROP_STREAM0 + 1, self.keep)
+                fn = K.decode_persistent_hist_spk_dropout if hist else \
+                    K.decode_persistent_spk_dropout
+                launch = functools.partial(fn, *pre, *spk, self.seed, DROP_STREAM0 + 1,
+                                           self.keep)
             else:
-                launch = functools.partial(K.decode_persistent_spk, *spk)
+                fn = K.decode_persistent_hist_spk if hist else K.decode_persistent_spk
+                launch = functools.partial(fn, *pre, *spk)
         elif self.drop:     # both prenet layers drop
-            launch = functools.partial(K.decode_persistent_dropout, self.seed, DROP_STREAM0,
-                                       DROP_STREAM0 + 1, self.keep)
+            fn = K.decode_persistent_hist_dropout if hist else K.decode_persistent_dropout
+            launch = functools.partial(fn, *pre, self.seed, DROP_STREAM0, DROP_STREAM0 + 1,
+                                       self.keep)
+        elif hist:
+            launch = functools.partial(K.decode_persistent_hist, *pre)
         else:
             launch = K.decode_persistent
         launch(
@@ -327,8 +373,8 @@ class FreeRunningDecoder:
             locW=P[f"{a1}/location_layer/kernel"], v2=P[f"{a2}/attention_v"],
             W1=P["decoder/lstm1/kernel"], bl1=P["decoder/lstm1/bias"],
             W2=P["decoder/lstm2/kernel"], bl2=P["decoder/lstm2/bias"],
-            Wqku=pk["Wqku"], bqku=pk["bqku"], bz=pk["bz"], Wms=pl.Wms, bms=pl.bms,
-            MS=pl.MS, AL1=pl.AL1, S2=pl.S2, SA_P=pl.SA_P[0], state=pl.state,
+            Wqku=pk["Wqku"], bqku=pk["bqku"], bz=pk["bz"], Wms=None if hist else pl.Wms,
+            bms=None if hist else pl.bms, MS=None if hist else pl.MS, AL1=pl.AL1, S2=pl.S2, SA_P=pl.SA_P[0], state=pl.state,
             scratch=pl.scratch, scratch_bytes=pl.scratch.numel(), err=pl.err)
 
     def _try_persistent(self, pl: _Plan, Tm: int) -> Optional[str]:
@@ -701,6 +747,8 @@ class FreeRunningDecoder:
                 first = int(pl.state.item()) if stop_mode else -1
                 if first >= 0:
                     steps = first + 1
+                if pl.ZH is not None:
+                    self._project_history(pl, steps)
             elif self.persistent:
                 raise _lib.SatLibraryError("sat_decode_persistent: " + why)
             else:

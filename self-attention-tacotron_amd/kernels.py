@@ -437,6 +437,60 @@ def decode_persistent_spk_dropout(spk0: torch.Tensor, Wd: torch.Tensor, bd: torc
         "sat_decode_persistent_spk_dropout")
 
 
+def _decode_desc(kw):
+    d = _lib.SatDecodePersistent()
+    for k, v in kw.items():
+        setattr(d, k, _p(v) if isinstance(v, torch.Tensor) or v is None else v)
+    return d
+
+
+def _decode_history(ZH, STOP, w_stop, b_stop):
+    h = _lib.SatDecodeHistory()
+    h.ZH, h.STOP, h.w_stop, h.b_stop = _p(ZH), _p(STOP), _p(w_stop), _p(b_stop)
+    return h
+
+
+def decode_persistent_hist(hist, **kw):
+    """sat_decode_persistent_hist: the one-launch decode for any output width.  ``hist`` =
+    (ZH [T, B, 256], STOP [T, B], w_stop [256], b_stop [1]): the kernel stores the head output
+    and the stop logit of every step, the caller projects ZH after the launch; Wms / bms / MS of
+    the base fields are unused."""
+    d, h = _decode_desc(kw), _decode_history(*hist)
+    _lib.check(_lib.load().sat_decode_persistent_hist(ctypes.byref(d), ctypes.byref(h), _stream()),
+               "sat_decode_persistent_hist")
+
+
+def decode_persistent_hist_dropout(hist, seed_dev: torch.Tensor, stream0: int, stream1: int,
+                                   keep: float, **kw):
+    """sat_decode_persistent_hist_dropout: the same with both prenet layers' dropout drawn inside
+    the kernel (arguments as decode_persistent_dropout)."""
+    d, h = _decode_desc(kw), _decode_history(*hist)
+    _lib.check(_lib.load().sat_decode_persistent_hist_dropout(
+        ctypes.byref(d), ctypes.byref(h), _p(seed_dev), stream0, stream1, keep, _stream()),
+        "sat_decode_persistent_hist_dropout")
+
+
+def decode_persistent_hist_spk(hist, spk0: torch.Tensor, Wd: torch.Tensor, bd: torch.Tensor,
+                               **kw):
+    """sat_decode_persistent_hist_spk: the history decode of the multi-speaker decoder
+    (arguments as decode_persistent_spk)."""
+    d, h, s = _decode_desc(kw), _decode_history(*hist), _decode_speaker(spk0, Wd, bd)
+    _lib.check(_lib.load().sat_decode_persistent_hist_spk(
+        ctypes.byref(d), ctypes.byref(s), ctypes.byref(h), _stream()),
+        "sat_decode_persistent_hist_spk")
+
+
+def decode_persistent_hist_spk_dropout(hist, spk0: torch.Tensor, Wd: torch.Tensor,
+                                       bd: torch.Tensor, seed_dev: torch.Tensor, stream1: int,
+                                       keep: float, **kw):
+    """sat_decode_persistent_hist_spk_dropout: the same under apply_dropout_on_inference (only
+    prenet layer 1 drops; arguments as decode_persistent_spk_dropout)."""
+    d, h, s = _decode_desc(kw), _decode_history(*hist), _decode_speaker(spk0, Wd, bd)
+    _lib.check(_lib.load().sat_decode_persistent_hist_spk_dropout(
+        ctypes.byref(d), ctypes.byref(s), ctypes.byref(h), _p(seed_dev), stream1, keep,
+        _stream()), "sat_decode_persistent_hist_spk_dropout")
+
+
 def stop_check(stop: torch.Tensor, t: int, min_iters: int, state: torch.Tensor):
     """state[0] := t if (no earlier finish) and t > min_iters and all sigmoid(stop) > 0.5."""
     _lib.call("sat_stop_check", _p(stop), stop.stride(0), stop.shape[0], t, min_iters,
