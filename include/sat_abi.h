@@ -375,70 +375,60 @@ typedef struct SatDecodePersistent {
   int64_t* prof;   /* nullable: per-workgroup phase clocks of the -DSAT_DP_TRACE build */
 } SatDecodePersistent;
 int64_t sat_decode_persistent_scratch_bytes(void);
-int sat_decode_persistent(const SatDecodePersistent* a, void* stream);
-/* The same decode with the decoder prenets' dropout kept on (apply_dropout_on_inference; the
- * reference hands the switch to its PreNets, modules/module.py:1511-1517): after the ReLU, prenet
- * layer l's output (t, b, col) is multiplied by the value sat_rng_fill(seed_ptr, stream_l, keep,
- * 1 / keep) writes at element (t*B + b)*P_l + col of a step-major [T][B][P_l] tensor (P_0 = 256,
- * P_1 = 128).  The words are drawn inside the kernel, one Philox call per produced element; no
- * mask touches memory.  seed_ptr[0] is read by the launch and left unchanged (the caller advances
- * it, sat_counter_add).  A separate kernel instantiation: sat_decode_persistent is unaffected. */
-int sat_decode_persistent_dropout(const SatDecodePersistent* a, const uint64_t* seed_ptr,
-                                  uint64_t stream0, uint64_t stream1, float keep, void* stream);
-/* The same decode for the multi-speaker decoder (use_speaker_embedding with
- * speaker_embedd_to_prenet: hparams.py vctk preset).  Prenet layer 0 is the MultiSpeakerPreNet
+/* Prenet dropout kept on (apply_dropout_on_inference; the reference hands the switch to its
+ * PreNets, modules/module.py:1511-1517): after the ReLU, prenet layer l's output (t, b, col) is
+ * multiplied by the value sat_rng_fill(seed, stream_l, keep, 1 / keep) writes at element
+ * (t*B + b)*P_l + col of a step-major [T][B][P_l] tensor (P_0 = 256, P_1 = 128).  The words are
+ * drawn inside the kernel, one Philox call per produced element; no mask touches memory.
+ * seed[0] is read by the launch and left unchanged (the caller advances it, sat_counter_add).
+ * With a speaker struct only prenet layer 1 drops (the MultiSpeakerPreNet drops under
+ * is_training only), so stream0 is unread there. */
+typedef struct SatDecodeDropout {
+  const uint64_t* seed;          /* device word */
+  uint64_t stream0, stream1;     /* Philox stream ids of the layer 0 / layer 1 masks */
+  float keep;                    /* keep probability, > 0 */
+} SatDecodeDropout;
+/* The multi-speaker decoder (use_speaker_embedding with speaker_embedd_to_prenet: hparams.py
+ * vctk preset).  Prenet layer 0 is the MultiSpeakerPreNet
  * (modules/multi_speaker_modules.py:27-32):
  *   d0 = relu(x W_dense0 + b_dense0) + softsign(s_b W_sp + b_sp),  y0 = relu(d0 W_dense + b_dense)
  * SatDecodePersistent carries the dense0 fold (Wzp = W_out[:, 80:160] W_dense0,
  * bzp = b_out[80:160] W_dense0 + b_dense0, bp0 = b_dense0); spk0 is the softsign row of every
  * utterance (constant over the decode, formed by the caller), Wd / bd the second dense.  One more
- * phase and hand-off per step; everything after prenet layer 0 is the single-speaker decode.
- * _spk_dropout: apply_dropout_on_inference -- only prenet layer 1 drops (the MultiSpeakerPreNet
- * drops under is_training only), its mask the [T][B][128] draw on stream1 as above.
- * Separate kernel instantiations: the two entries above are unaffected.  The scratch of
- * sat_decode_persistent_scratch_bytes() serves all four. */
+ * phase and hand-off per step; everything after prenet layer 0 is the single-speaker decode. */
 typedef struct SatDecodeSpeaker {
   const float* spk0;   /* [B][256] */
   const float* Wd;     /* [256][256] */
   const float* bd;     /* [256] */
 } SatDecodeSpeaker;
-int sat_decode_persistent_spk(const SatDecodePersistent* a, const SatDecodeSpeaker* s,
-                              void* stream);
-int sat_decode_persistent_spk_dropout(const SatDecodePersistent* a, const SatDecodeSpeaker* s,
-                                      const uint64_t* seed_ptr, uint64_t stream1, float keep,
-                                      void* stream);
-/* The same decode for any output width (num_mels x outputs_per_step; the VQ-code corpora have
- * num_mels = num_codes, r = 1: hparams.py codes preset, codes/dataset.py).  Only two things in a
- * step depend on the output projection -- the stop column and the fed frame, and the caller folds
- * the fed frame into the first prenet layer (Wzp = W_out[:, -feed:] W_p0, bzp = b_out[-feed:] W_p0
- * + b_p0, feed = num_mels: with r = 1 the whole projection).  So the step forms the stop value
- * alone, stop = z . w_stop + b_stop, and stores the head output z of every step; the caller
- * projects the history once after the launch (mel[:steps] = ZH[:steps] W_out + b_out, one GEMM).
+/* Any output width (num_mels x outputs_per_step; the VQ-code corpora have num_mels = num_codes,
+ * r = 1: hparams.py codes preset, codes/dataset.py).  Only two things in a step depend on the
+ * output projection -- the stop column and the fed frame, and the caller folds the fed frame into
+ * the first prenet layer (Wzp = W_out[:, -feed:] W_p0, bzp = b_out[-feed:] W_p0 + b_p0,
+ * feed = num_mels: with r = 1 the whole projection).  So the step forms the stop value alone,
+ * stop = z . w_stop + b_stop, and stores the head output z of every step; the caller projects the
+ * history once after the launch (mel[:steps] = ZH[:steps] W_out + b_out, one GEMM).
  *   ZH[t][b][0:256]  the z row of step t (16-byte aligned),  STOP[t][b]  its stop logit;
  *   w_stop [256], b_stop [1]  the stop projection (stop_token_projection kernel / bias).
- * Rows after the first finished step are left unwritten, as those of MS are.  Wms, bms
- * and MS of SatDecodePersistent are unused here and may be null; every other field, the stop
- * test, state, err and the scratch of sat_decode_persistent_scratch_bytes() are as above.
- * _hist / _hist_dropout / _hist_spk / _hist_spk_dropout mirror the four entries above argument
- * for argument.  Separate kernel instantiations in a module of their own: the four entries above
- * are unaffected. */
+ * Rows after the first finished step are left unwritten, as those of MS are.  Wms, bms and MS of
+ * SatDecodePersistent are unused here and may be null; every other field, the stop test, state,
+ * err and the scratch are as above. */
 typedef struct SatDecodeHistory {
   float* ZH;              /* [T][B][256] */
   float* STOP;            /* [T][B] */
   const float* w_stop;    /* [256] */
   const float* b_stop;    /* [1] */
 } SatDecodeHistory;
-int sat_decode_persistent_hist(const SatDecodePersistent* a, const SatDecodeHistory* h,
-                               void* stream);
-int sat_decode_persistent_hist_dropout(const SatDecodePersistent* a, const SatDecodeHistory* h,
-                                       const uint64_t* seed_ptr, uint64_t stream0,
-                                       uint64_t stream1, float keep, void* stream);
-int sat_decode_persistent_hist_spk(const SatDecodePersistent* a, const SatDecodeSpeaker* s,
-                                   const SatDecodeHistory* h, void* stream);
-int sat_decode_persistent_hist_spk_dropout(const SatDecodePersistent* a,
-                                           const SatDecodeSpeaker* s, const SatDecodeHistory* h,
-                                           const uint64_t* seed_ptr, uint64_t stream1, float keep,
-                                           void* stream);
+/* The one entry.  Each non-null option struct switches its variant on; every combination is a
+ * kernel instantiation of its own (a null option leaves no trace in the kernel that runs), and
+ * the scratch of sat_decode_persistent_scratch_bytes() serves all eight.  Arguments are checked
+ * in a fixed order -- shape, hist, spk, drop, the base struct's pointers, scratch size,
+ * alignments -- before any device is touched; a message about an option struct names it. */
+int sat_decode_persistent(const SatDecodePersistent* a,
+                          const SatDecodeDropout* drop,   /* NULL: no prenet dropout       */
+                          const SatDecodeSpeaker* spk,    /* NULL: single-speaker prenet   */
+                          const SatDecodeHistory* hist,   /* NULL: mel-row (80 x 2) output */
+                          void* stream);
 
 /* ---------------------------------------------------------------- (Zoneout)LSTM step
  * One time step of TF LSTMCell wrapped in ext tacotron2 ZoneoutLSTMCell,

@@ -69,8 +69,8 @@ _I32, _I64, _U64, _F = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c
 
 
 def _struct(name, spec):
-    """spec: 'type:field ...' with types i32 i64 f32 ptr."""
-    tmap = {"i32": _I32, "i64": _I64, "f32": _F, "ptr": _P}
+    """spec: 'type:field ...' with types i32 i64 u64 f32 ptr."""
+    tmap = {"i32": _I32, "i64": _I64, "u64": _U64, "f32": _F, "ptr": _P}
     fields = [(f, tmap[t]) for t, f in (item.split(":") for item in spec.split())]
     return type(name, (ctypes.Structure,), {"_fields_": fields})
 
@@ -163,6 +163,8 @@ SatDecodePersistent = _struct("SatDecodePersistent", """
     ptr:Wqku ptr:bqku ptr:bz ptr:Wms ptr:bms ptr:MS ptr:AL1 ptr:S2 ptr:SA_P ptr:state
     ptr:scratch i64:scratch_bytes ptr:err ptr:prof""")
 
+SatDecodeDropout = _struct("SatDecodeDropout", "ptr:seed u64:stream0 u64:stream1 f32:keep")
+
 SatDecodeSpeaker = _struct("SatDecodeSpeaker", "ptr:spk0 ptr:Wd ptr:bd")
 
 SatDecodeHistory = _struct("SatDecodeHistory", "ptr:ZH ptr:STOP ptr:w_stop ptr:b_stop")
@@ -254,25 +256,9 @@ SIGNATURES = {
     "sat_decoder_loop_bwd": [ctypes.POINTER(SatDecoderLoopBwd), _P],
     "sat_decode_attention_step": [_P, _I64, _I64, _I32, _I32, _I32, _I32, _F, _P, _I32, _P,
                                   _I64, _P],
-    "sat_decode_persistent": [ctypes.POINTER(SatDecodePersistent), _P],
-    "sat_decode_persistent_dropout": [ctypes.POINTER(SatDecodePersistent), _P, _U64, _U64, _F,
-                                      _P],
-    "sat_decode_persistent_spk": [ctypes.POINTER(SatDecodePersistent),
-                                  ctypes.POINTER(SatDecodeSpeaker), _P],
-    "sat_decode_persistent_spk_dropout": [ctypes.POINTER(SatDecodePersistent),
-                                          ctypes.POINTER(SatDecodeSpeaker), _P, _U64, _F, _P],
-    "sat_decode_persistent_hist": [ctypes.POINTER(SatDecodePersistent),
-                                   ctypes.POINTER(SatDecodeHistory), _P],
-    "sat_decode_persistent_hist_dropout": [ctypes.POINTER(SatDecodePersistent),
-                                           ctypes.POINTER(SatDecodeHistory), _P, _U64, _U64, _F,
-                                           _P],
-    "sat_decode_persistent_hist_spk": [ctypes.POINTER(SatDecodePersistent),
-                                       ctypes.POINTER(SatDecodeSpeaker),
-                                       ctypes.POINTER(SatDecodeHistory), _P],
-    "sat_decode_persistent_hist_spk_dropout": [ctypes.POINTER(SatDecodePersistent),
-                                               ctypes.POINTER(SatDecodeSpeaker),
-                                               ctypes.POINTER(SatDecodeHistory), _P, _U64, _F,
-                                               _P],
+    "sat_decode_persistent": [ctypes.POINTER(SatDecodePersistent),
+                              ctypes.POINTER(SatDecodeDropout), ctypes.POINTER(SatDecodeSpeaker),
+                              ctypes.POINTER(SatDecodeHistory), _P],
     "sat_zlstm_step_fwd": [ctypes.POINTER(SatLstmFwd), _P],
     "sat_zlstm_step_bwd": [ctypes.POINTER(SatLstmBwd), _P],
     "sat_attn_param_grad_rows": [_I32, _I32],

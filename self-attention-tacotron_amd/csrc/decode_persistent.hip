@@ -181,7 +181,7 @@ struct SpkArgs<true> {
   SatDecodeSpeaker s;
 };
 
-// The history variant (kHist = true: sat_decode_persistent_hist*).  Only two things in a step
+// The history variant (kHist = true: a SatDecodeHistory is given).  Only two things in a step
 // depend on the output projection: the stop column and the fed frame, and the fed frame is folded
 // into Wzp by the caller.  So P1 forms the stop value alone (workgroup 0 of the group, wave 0) and
 // stores the gathered z_{t-1} row to ZH[t-1][b]; Wms / bms / MS of SatDecodePersistent are
@@ -845,38 +845,25 @@ __global__ void __launch_bounds__(kTh) decode_persistent_kernel(SatDecodePersist
 
 using namespace sat;
 
-// The entries live in three modules built from this one source: the single-speaker pair here, the
-// multi-speaker pair in decode_persistent_spk.hip (which defines SAT_DP_SPK and includes this
-// file), the four history entries in decode_persistent_hist.hip (SAT_DP_HIST).  One module holding
-// all the kernels compiles the single-speaker pair to another instruction stream than the module
-// without the others does; apart, adding kernels leaves the existing ones exactly as they were
-// (`make asm`).
+// The eight kernels live in three modules built from this one source: the single-speaker pair
+// here, the multi-speaker pair in decode_persistent_spk.hip (which defines SAT_DP_SPK and includes
+// this file), the four history kernels in decode_persistent_hist.hip (SAT_DP_HIST).  One module
+// holding all the kernels compiles the single-speaker pair to another instruction stream than the
+// module without the others does; apart, adding kernels leaves the existing ones exactly as they
+// were (`make asm`).  Each module exports one launch function over the
+// kernels it owns (persistent.h); the one entry, sat_decode_persistent at the end of this file,
+// checks the arguments and calls the module the option structs select.
 #if !defined(SAT_DP_SPK) && !defined(SAT_DP_HIST)
 extern "C" int64_t sat_decode_persistent_scratch_bytes(void) {
   return (kZeroDwords + kCacheFloats + kD0Dwords) * 4;
 }
 #endif
 
-// Argument checks, co-residency test, scratch clear and launch shared by every entry.
+// Co-residency test, scratch clear and launch of one kernel; sat_decode_persistent has checked
+// the arguments.
 template <bool kDrop, bool kSpk, bool kHist>
 static int launch_decode(const SatDecodePersistent* a, const DropArgs<kDrop>& args,
                          const SpkArgs<kSpk>& spk, const HistArgs<kHist>& hist, void* stream) {
-  SAT_CHECK_ARG(a && a->B >= 1 && a->B <= kG && a->N >= 1 && a->N <= kNM && a->T >= 1 &&
-                    a->T <= kW * kRM,
-                "sat_decode_persistent: B <= 8, N <= 256, T <= 512 (got B=%d N=%d T=%d)",
-                a ? a->B : 0, a ? a->N : 0, a ? a->T : 0);
-  // the mel-row entries write MS through Wms / bms; the history entries leave the three unused
-  SAT_CHECK_ARG(a->lengths && a->K1 && a->V1 && a->K2 && a->V2 && a->Wzp && a->bzp && a->bp0 &&
-                    a->Wp1 && a->bp1 && a->W0 && a->b0 && a->Wq && a->b1 && a->v1 && a->convW &&
-                    a->convb && a->locW && a->v2 && a->W1 && a->bl1 && a->W2 && a->bl2 &&
-                    a->Wqku && a->bqku && a->bz && (kHist || (a->Wms && a->bms && a->MS)) &&
-                    a->AL1 && a->S2 && a->state && a->scratch && a->err,
-                "sat_decode_persistent: null pointer");
-  SAT_CHECK_ARG(a->scratch_bytes >= sat_decode_persistent_scratch_bytes(),
-                "sat_decode_persistent: scratch too small");
-  SAT_CHECK_ARG(aligned16(a->W0) && aligned16(a->W1) && aligned16(a->W2) && aligned16(a->b0) &&
-                    aligned16(a->bl1) && aligned16(a->bl2) && aligned16(a->scratch),
-                "sat_decode_persistent: LSTM weights / biases / scratch must be 16-byte aligned");
   int dev = 0, cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -903,113 +890,76 @@ static int launch_decode(const SatDecodePersistent* a, const DropArgs<kDrop>& ar
   return SAT_OK;
 }
 
-static void drop_args(const uint64_t* seed_ptr, uint64_t stream0, uint64_t stream1, float keep,
-                      DropArgs<true>* args) {
-  args->seed = seed_ptr;
-  args->stream0 = stream0;
-  args->stream1 = stream1;
-  args->keep = keep;
-  args->on = (float)(1.0 / (double)keep);
-}
-
-#if !defined(SAT_DP_SPK) && !defined(SAT_DP_HIST)
-extern "C" int sat_decode_persistent(const SatDecodePersistent* a, void* stream) {
-  return launch_decode<false, false, false>(a, DropArgs<false>{}, SpkArgs<false>{},
-                                            HistArgs<false>{}, stream);
-}
-
-extern "C" int sat_decode_persistent_dropout(const SatDecodePersistent* a, const uint64_t* seed_ptr,
-                                             uint64_t stream0, uint64_t stream1, float keep,
-                                             void* stream) {
-  SAT_CHECK_ARG(a && seed_ptr, "sat_decode_persistent_dropout: null pointer");
-  SAT_CHECK_ARG(keep > 0.f, "sat_decode_persistent_dropout: keep must be > 0 (got %g)",
-                (double)keep);
+// The kDrop pair of one (kSpk, kHist): a null option struct selects the kernel without the draw.
+template <bool kSpk, bool kHist>
+static int launch_drop(const SatDecodePersistent* a, const SatDecodeDropout* drop,
+                       const SpkArgs<kSpk>& spk, const HistArgs<kHist>& hist, void* stream) {
+  if (!drop) return launch_decode<false, kSpk, kHist>(a, DropArgs<false>{}, spk, hist, stream);
   DropArgs<true> args;
-  drop_args(seed_ptr, stream0, stream1, keep, &args);
-  return launch_decode<true, false, false>(a, args, SpkArgs<false>{}, HistArgs<false>{}, stream);
+  args.seed = drop->seed;
+  args.stream0 = drop->stream0;   // unread by the kSpk kernels: layer 0 never drops there
+  args.stream1 = drop->stream1;
+  args.keep = drop->keep;
+  args.on = (float)(1.0 / (double)drop->keep);
+  return launch_decode<true, kSpk, kHist>(a, args, spk, hist, stream);
+}
+
+#if defined(SAT_DP_HIST)
+int sat::decode_persistent_hist_launch(const SatDecodePersistent* a, const SatDecodeDropout* drop,
+                                       const SatDecodeSpeaker* spk, const SatDecodeHistory* hist,
+                                       void* stream) {
+  // (the module's kernels are emitted in the order they are first named here)
+  const HistArgs<true> h{*hist};
+  if (!spk) return launch_drop<false, true>(a, drop, SpkArgs<false>{}, h, stream);
+  return launch_drop<true, true>(a, drop, SpkArgs<true>{*spk}, h, stream);
 }
 #elif defined(SAT_DP_SPK)
-
-extern "C" int sat_decode_persistent_spk(const SatDecodePersistent* a, const SatDecodeSpeaker* sp,
-                                         void* stream) {
-  SAT_CHECK_ARG(a && sp && sp->spk0 && sp->Wd && sp->bd, "sat_decode_persistent_spk: null pointer");
-  SpkArgs<true> spk;
-  spk.s = *sp;
-  return launch_decode<false, true, false>(a, DropArgs<false>{}, spk, HistArgs<false>{}, stream);
-}
-
-extern "C" int sat_decode_persistent_spk_dropout(const SatDecodePersistent* a,
-                                                 const SatDecodeSpeaker* sp,
-                                                 const uint64_t* seed_ptr, uint64_t stream1,
-                                                 float keep, void* stream) {
-  SAT_CHECK_ARG(a && sp && sp->spk0 && sp->Wd && sp->bd && seed_ptr,
-                "sat_decode_persistent_spk_dropout: null pointer");
-  SAT_CHECK_ARG(keep > 0.f, "sat_decode_persistent_spk_dropout: keep must be > 0 (got %g)",
-                (double)keep);
-  DropArgs<true> args;
-  drop_args(seed_ptr, 0, stream1, keep, &args);   // stream0: layer 0 never drops here
-  SpkArgs<true> spk;
-  spk.s = *sp;
-  return launch_decode<true, true, false>(a, args, spk, HistArgs<false>{}, stream);
+int sat::decode_persistent_spk_launch(const SatDecodePersistent* a, const SatDecodeDropout* drop,
+                                      const SatDecodeSpeaker* spk, void* stream) {
+  return launch_drop<true, false>(a, drop, SpkArgs<true>{*spk}, HistArgs<false>{}, stream);
 }
 #else
-
-// ---- the history entries (kHist = true): the shape check first, as in every entry, then the
-// history struct's own pointers; nothing is launched on a bad argument
-#define SAT_DP_HIST_CHECK(name)                                                                  \
-  SAT_CHECK_ARG(a && a->B >= 1 && a->B <= kG && a->N >= 1 && a->N <= kNM && a->T >= 1 &&        \
-                    a->T <= kW * kRM,                                                            \
-                name ": B <= 8, N <= 256, T <= 512 (got B=%d N=%d T=%d)", a ? a->B : 0,          \
-                a ? a->N : 0, a ? a->T : 0);                                                     \
-  SAT_CHECK_ARG(h && h->ZH && h->STOP && h->w_stop && h->b_stop, name ": null pointer");         \
-  SAT_CHECK_ARG(aligned16(h->ZH), name ": ZH must be 16-byte aligned");                          \
-  HistArgs<true> hist;                                                                           \
-  hist.h = *h
-
-extern "C" int sat_decode_persistent_hist(const SatDecodePersistent* a, const SatDecodeHistory* h,
-                                          void* stream) {
-  SAT_DP_HIST_CHECK("sat_decode_persistent_hist");
-  return launch_decode<false, false, true>(a, DropArgs<false>{}, SpkArgs<false>{}, hist, stream);
+int sat::decode_persistent_launch(const SatDecodePersistent* a, const SatDecodeDropout* drop,
+                                  void* stream) {
+  return launch_drop<false, false>(a, drop, SpkArgs<false>{}, HistArgs<false>{}, stream);
 }
 
-extern "C" int sat_decode_persistent_hist_dropout(const SatDecodePersistent* a,
-                                                  const SatDecodeHistory* h,
-                                                  const uint64_t* seed_ptr, uint64_t stream0,
-                                                  uint64_t stream1, float keep, void* stream) {
-  SAT_DP_HIST_CHECK("sat_decode_persistent_hist_dropout");
-  SAT_CHECK_ARG(seed_ptr, "sat_decode_persistent_hist_dropout: null pointer");
-  SAT_CHECK_ARG(keep > 0.f, "sat_decode_persistent_hist_dropout: keep must be > 0 (got %g)",
-                (double)keep);
-  DropArgs<true> args;
-  drop_args(seed_ptr, stream0, stream1, keep, &args);
-  return launch_decode<true, false, true>(a, args, SpkArgs<false>{}, hist, stream);
+// The one entry: every argument check, once and in this order, before any device is touched;
+// then the module that owns the selected kernel.
+extern "C" int sat_decode_persistent(const SatDecodePersistent* a, const SatDecodeDropout* drop,
+                                     const SatDecodeSpeaker* spk, const SatDecodeHistory* hist,
+                                     void* stream) {
+  SAT_CHECK_ARG(a && a->B >= 1 && a->B <= kG && a->N >= 1 && a->N <= kNM && a->T >= 1 &&
+                    a->T <= kW * kRM,
+                "sat_decode_persistent: B <= 8, N <= 256, T <= 512 (got B=%d N=%d T=%d)",
+                a ? a->B : 0, a ? a->N : 0, a ? a->T : 0);
+  if (hist) {
+    SAT_CHECK_ARG(hist->ZH && hist->STOP && hist->w_stop && hist->b_stop,
+                  "sat_decode_persistent: hist: null pointer");
+    SAT_CHECK_ARG(aligned16(hist->ZH), "sat_decode_persistent: hist: ZH must be 16-byte aligned");
+  }
+  if (spk)
+    SAT_CHECK_ARG(spk->spk0 && spk->Wd && spk->bd, "sat_decode_persistent: spk: null pointer");
+  if (drop) {
+    SAT_CHECK_ARG(drop->seed, "sat_decode_persistent: drop: null pointer");
+    SAT_CHECK_ARG(drop->keep > 0.f, "sat_decode_persistent: drop: keep must be > 0 (got %g)",
+                  (double)drop->keep);
+  }
+  // the mel-row kernels write MS through Wms / bms; the history kernels leave the three unused
+  SAT_CHECK_ARG(a->lengths && a->K1 && a->V1 && a->K2 && a->V2 && a->Wzp && a->bzp && a->bp0 &&
+                    a->Wp1 && a->bp1 && a->W0 && a->b0 && a->Wq && a->b1 && a->v1 && a->convW &&
+                    a->convb && a->locW && a->v2 && a->W1 && a->bl1 && a->W2 && a->bl2 &&
+                    a->Wqku && a->bqku && a->bz && (hist || (a->Wms && a->bms && a->MS)) &&
+                    a->AL1 && a->S2 && a->state && a->scratch && a->err,
+                "sat_decode_persistent: null pointer");
+  SAT_CHECK_ARG(a->scratch_bytes >= sat_decode_persistent_scratch_bytes(),
+                "sat_decode_persistent: scratch too small");
+  SAT_CHECK_ARG(aligned16(a->W0) && aligned16(a->W1) && aligned16(a->W2) && aligned16(a->b0) &&
+                    aligned16(a->bl1) && aligned16(a->bl2) && aligned16(a->scratch),
+                "sat_decode_persistent: LSTM weights / biases / scratch must be 16-byte aligned");
+  if (hist) return decode_persistent_hist_launch(a, drop, spk, hist, stream);
+  if (spk) return decode_persistent_spk_launch(a, drop, spk, stream);
+  return decode_persistent_launch(a, drop, stream);
 }
-
-extern "C" int sat_decode_persistent_hist_spk(const SatDecodePersistent* a,
-                                              const SatDecodeSpeaker* sp,
-                                              const SatDecodeHistory* h, void* stream) {
-  SAT_DP_HIST_CHECK("sat_decode_persistent_hist_spk");
-  SAT_CHECK_ARG(sp && sp->spk0 && sp->Wd && sp->bd, "sat_decode_persistent_hist_spk: null pointer");
-  SpkArgs<true> spk;
-  spk.s = *sp;
-  return launch_decode<false, true, true>(a, DropArgs<false>{}, spk, hist, stream);
-}
-
-extern "C" int sat_decode_persistent_hist_spk_dropout(const SatDecodePersistent* a,
-                                                      const SatDecodeSpeaker* sp,
-                                                      const SatDecodeHistory* h,
-                                                      const uint64_t* seed_ptr, uint64_t stream1,
-                                                      float keep, void* stream) {
-  SAT_DP_HIST_CHECK("sat_decode_persistent_hist_spk_dropout");
-  SAT_CHECK_ARG(sp && sp->spk0 && sp->Wd && sp->bd && seed_ptr,
-                "sat_decode_persistent_hist_spk_dropout: null pointer");
-  SAT_CHECK_ARG(keep > 0.f, "sat_decode_persistent_hist_spk_dropout: keep must be > 0 (got %g)",
-                (double)keep);
-  DropArgs<true> args;
-  drop_args(seed_ptr, 0, stream1, keep, &args);   // stream0: layer 0 never drops here
-  SpkArgs<true> spk;
-  spk.s = *sp;
-  return launch_decode<true, true, true>(a, args, spk, hist, stream);
-}
-#undef SAT_DP_HIST_CHECK
 #endif
+

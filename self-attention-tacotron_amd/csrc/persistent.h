@@ -277,4 +277,14 @@ bool dec_attn_fwd8_eligible(const SatDecAttnFwd* a);
 int dec_attn_fwd8_launch(const SatDecAttnFwd* a, hipStream_t s);
 bool dec_attn_bwd8_eligible(const SatDecAttnBwd* a);   // decoder_persistent8_bwd.hip
 int dec_attn_bwd8_launch(const SatDecAttnBwd* a, hipStream_t s);
+// the one-launch decode's three modules (decode_persistent.hip and its two includers): each
+// launches the kernels it owns -- the kDrop pair; drop null: no draw, spk null: single speaker --
+// on arguments sat_decode_persistent has checked
+int decode_persistent_launch(const SatDecodePersistent* a, const SatDecodeDropout* drop,
+                             void* stream);
+int decode_persistent_spk_launch(const SatDecodePersistent* a, const SatDecodeDropout* drop,
+                                 const SatDecodeSpeaker* spk, void* stream);
+int decode_persistent_hist_launch(const SatDecodePersistent* a, const SatDecodeDropout* drop,
+                                  const SatDecodeSpeaker* spk, const SatDecodeHistory* hist,
+                                  void* stream);
 }  // namespace sat

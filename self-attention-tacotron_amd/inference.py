@@ -50,8 +50,8 @@ the MultiSpeakerPreNet (layer 0 under ``speaker_embedd_to_prenet``) drops under 
 only and so stays clean.  The launch path fills the masks of the whole decode in one
 ``sat_rng_fill_segments`` launch before the loop (outside any captured graph) and multiplies row
 t in as the prenet products' ``mul`` epilogue; the one-launch decode draws the same words inside
-the kernel (``sat_decode_persistent_dropout``; ``sat_decode_persistent_spk_dropout`` for the
-multi-speaker decoder, where only layer 1 draws).  Every ``run()`` advances the seed by one on the
+the kernel (``sat_decode_persistent`` with its ``SatDecodeDropout`` option; with the speaker option
+of the multi-speaker decoder only layer 1 draws).  Every ``run()`` advances the seed by one on the
 device (``sat_counter_add``); the seed is not part of a checkpoint.
 
 Every arithmetic op is a libsat_hip kernel; torch allocates, views and copies.
@@ -60,7 +60,6 @@ Every arithmetic op is a libsat_hip kernel; torch allocates, views and copies.
 from __future__ import annotations
 
 import ctypes
-import functools
 import math
 import warnings
 from typing import Dict, Optional
@@ -78,7 +77,7 @@ DROP_STREAM0 = 1001
 
 
 def drop_on_value(keep: float) -> float:
-    """The value of a surviving element, 1 / keep, as sat_decode_persistent_dropout forms it:
+    """The value of a surviving element, 1 / keep, as sat_decode_persistent forms it:
     the double quotient of the float32 ``keep``, rounded to float32 at the call."""
     return 1.0 / ctypes.c_float(keep).value
 
@@ -141,11 +140,11 @@ class FreeRunningDecoder:
     dimensions -- single speaker, or the speaker embedding fed to the prenet only
     (``speaker_embedd_to_prenet``; not ``speaker_embedd_to_decoder``) --, no transition agent or
     cumulative weights, one fed frame, B <= 8, N <= 256, T' <= 512), True requires it, False
-    keeps the per-step launches.  80 mels x r = 2 runs the mel-row entries (an 80-mel model
+    keeps the per-step launches.  80 mels x r = 2 runs the mel-row kernels (an 80-mel model
     with another r stays on the per-step launches), any other ``num_mels`` with any
     ``outputs_per_step`` (the codes corpora: ``num_mels = num_codes``, r = 1) the history
-    entries (``sat_decode_persistent_hist*``), which store the head output of every step and
-    leave the projection to one product after the launch.
+    kernels (the entry's ``SatDecodeHistory`` option), which store the head output of every
+    step and leave the projection to one product after the launch.
     ``seed``: the seed of the prenet masks under ``apply_dropout_on_inference`` -- an int (a
     device word of its own is made) or a one-element int64 device tensor the caller shares
     between decoders; every ``run()`` advances it by one.  Unused with the switch off.  With the
@@ -331,35 +330,21 @@ class FreeRunningDecoder:
         self._pack_persistent(pl)
         pk = pl.pk
         p0 = "decoder/prenet0"
-        # the history entries (any output width) take the same arguments behind their struct
-        # and no mel-row fields; the 80 x 2 models keep the mel-row entries
-        hist = pl.ZH is not None
-        pre = ()
-        if hist:
+        # the three options of the one entry.  History (any output width): the kernel keeps z
+        # and the stop logits and takes no mel-row fields; the 80 x 2 models keep the mel rows
+        hist = spk = drop = None
+        if pl.ZH is not None:
             st = "decoder/stop_token_projection"
-            pre = ((pl.ZH, pl.STOPH, P[f"{st}/kernel"], P[f"{st}/bias"]),)
+            hist = (pl.ZH, pl.STOPH, P[f"{st}/kernel"], P[f"{st}/bias"])
         if d.multi_speaker:
             # layer 0 = MultiSpeakerPreNet: pl.sp is the softsign row _prepare formed for both
             # paths; under the dropout switch only layer 1 drops (prenet_drops)
             p0, ms = "decoder/prenet0/dense0", "decoder/prenet0/dense"
             spk = (pl.sp, P[f"{ms}/kernel"], P[f"{ms}/bias"])
-            if self.drop:
-                fn = K.decode_persistent_hist_spk_dropout if hist else \
-                    K.decode_persistent_spk_dropout
-                launch = functools.partial(fn, *pre, *spk, self.seed, DROP_STREAM0 + 1,
-                                           self.keep)
-            else:
-                fn = K.decode_persistent_hist_spk if hist else K.decode_persistent_spk
-                launch = functools.partial(fn, *pre, *spk)
-        elif self.drop:     # both prenet layers drop
-            fn = K.decode_persistent_hist_dropout if hist else K.decode_persistent_dropout
-            launch = functools.partial(fn, *pre, self.seed, DROP_STREAM0, DROP_STREAM0 + 1,
-                                       self.keep)
-        elif hist:
-            launch = functools.partial(K.decode_persistent_hist, *pre)
-        else:
-            launch = K.decode_persistent
-        launch(
+        if self.drop:
+            drop = (self.seed, DROP_STREAM0, DROP_STREAM0 + 1, self.keep)
+        K.decode_persistent(
+            hist=hist, spk=spk, drop=drop,
             B=pl.B, N=pl.N, T=Tm, min_iters=self.min_iters,
             stop_mode=1 if self.helper == "stop_token" else 0,
             zc=hp.zoneout_factor_cell, zh=hp.zoneout_factor_output, u=0.5,

@@ -383,112 +383,36 @@ def decode_persistent_scratch_bytes() -> int:
     return int(_lib.load().sat_decode_persistent_scratch_bytes())
 
 
-def decode_persistent(**kw):
-    """sat_decode_persistent: the whole free-running decode as one launch (tensor arguments by
-    the SatDecodePersistent field names, scalars as ints / floats)."""
-    d = _lib.SatDecodePersistent()
-    for k, v in kw.items():
+def _decode_desc(st, names, values):
+    """byref of the struct ``st`` filled from ``values`` (tensors as pointers); None for None."""
+    if values is None:
+        return None
+    d = st()
+    for k, v in zip(names, values):
         setattr(d, k, _p(v) if isinstance(v, torch.Tensor) or v is None else v)
-    _lib.check(_lib.load().sat_decode_persistent(ctypes.byref(d), _stream()),
-               "sat_decode_persistent")
+    return ctypes.byref(d)
 
 
-def decode_persistent_dropout(seed_dev: torch.Tensor, stream0: int, stream1: int, keep: float,
-                              **kw):
-    """sat_decode_persistent_dropout: sat_decode_persistent with the prenet dropout of
-    apply_dropout_on_inference drawn inside the kernel (``seed_dev``: the uint64 seed word in
-    device memory; ``stream0`` / ``stream1``: the Philox stream ids of the two prenet layers)."""
-    d = _lib.SatDecodePersistent()
-    for k, v in kw.items():
-        setattr(d, k, _p(v) if isinstance(v, torch.Tensor) or v is None else v)
-    _lib.check(_lib.load().sat_decode_persistent_dropout(
-        ctypes.byref(d), _p(seed_dev), stream0, stream1, keep, _stream()),
-        "sat_decode_persistent_dropout")
-
-
-def _decode_speaker(spk0: torch.Tensor, Wd: torch.Tensor, bd: torch.Tensor):
-    s = _lib.SatDecodeSpeaker()
-    s.spk0, s.Wd, s.bd = _p(spk0), _p(Wd), _p(bd)
-    return s
-
-
-def decode_persistent_spk(spk0: torch.Tensor, Wd: torch.Tensor, bd: torch.Tensor, **kw):
-    """sat_decode_persistent_spk: sat_decode_persistent for the multi-speaker decoder (prenet
-    layer 0 = MultiSpeakerPreNet).  ``spk0`` [B, 256]: the softsign speaker row of every
-    utterance; ``Wd`` / ``bd``: the second dense; Wzp / bzp / bp0 carry the dense0 fold."""
-    d = _lib.SatDecodePersistent()
-    for k, v in kw.items():
-        setattr(d, k, _p(v) if isinstance(v, torch.Tensor) or v is None else v)
-    s = _decode_speaker(spk0, Wd, bd)
-    _lib.check(_lib.load().sat_decode_persistent_spk(ctypes.byref(d), ctypes.byref(s), _stream()),
-               "sat_decode_persistent_spk")
-
-
-def decode_persistent_spk_dropout(spk0: torch.Tensor, Wd: torch.Tensor, bd: torch.Tensor,
-                                  seed_dev: torch.Tensor, stream1: int, keep: float, **kw):
-    """sat_decode_persistent_spk_dropout: the same under apply_dropout_on_inference -- only
-    prenet layer 1 drops (``stream1``: the Philox stream id of its mask)."""
-    d = _lib.SatDecodePersistent()
-    for k, v in kw.items():
-        setattr(d, k, _p(v) if isinstance(v, torch.Tensor) or v is None else v)
-    s = _decode_speaker(spk0, Wd, bd)
-    _lib.check(_lib.load().sat_decode_persistent_spk_dropout(
-        ctypes.byref(d), ctypes.byref(s), _p(seed_dev), stream1, keep, _stream()),
-        "sat_decode_persistent_spk_dropout")
-
-
-def _decode_desc(kw):
-    d = _lib.SatDecodePersistent()
-    for k, v in kw.items():
-        setattr(d, k, _p(v) if isinstance(v, torch.Tensor) or v is None else v)
-    return d
-
-
-def _decode_history(ZH, STOP, w_stop, b_stop):
-    h = _lib.SatDecodeHistory()
-    h.ZH, h.STOP, h.w_stop, h.b_stop = _p(ZH), _p(STOP), _p(w_stop), _p(b_stop)
-    return h
-
-
-def decode_persistent_hist(hist, **kw):
-    """sat_decode_persistent_hist: the one-launch decode for any output width.  ``hist`` =
-    (ZH [T, B, 256], STOP [T, B], w_stop [256], b_stop [1]): the kernel stores the head output
-    and the stop logit of every step, the caller projects ZH after the launch; Wms / bms / MS of
-    the base fields are unused."""
-    d, h = _decode_desc(kw), _decode_history(*hist)
-    _lib.check(_lib.load().sat_decode_persistent_hist(ctypes.byref(d), ctypes.byref(h), _stream()),
-               "sat_decode_persistent_hist")
-
-
-def decode_persistent_hist_dropout(hist, seed_dev: torch.Tensor, stream0: int, stream1: int,
-                                   keep: float, **kw):
-    """sat_decode_persistent_hist_dropout: the same with both prenet layers' dropout drawn inside
-    the kernel (arguments as decode_persistent_dropout)."""
-    d, h = _decode_desc(kw), _decode_history(*hist)
-    _lib.check(_lib.load().sat_decode_persistent_hist_dropout(
-        ctypes.byref(d), ctypes.byref(h), _p(seed_dev), stream0, stream1, keep, _stream()),
-        "sat_decode_persistent_hist_dropout")
-
-
-def decode_persistent_hist_spk(hist, spk0: torch.Tensor, Wd: torch.Tensor, bd: torch.Tensor,
-                               **kw):
-    """sat_decode_persistent_hist_spk: the history decode of the multi-speaker decoder
-    (arguments as decode_persistent_spk)."""
-    d, h, s = _decode_desc(kw), _decode_history(*hist), _decode_speaker(spk0, Wd, bd)
-    _lib.check(_lib.load().sat_decode_persistent_hist_spk(
-        ctypes.byref(d), ctypes.byref(s), ctypes.byref(h), _stream()),
-        "sat_decode_persistent_hist_spk")
-
-
-def decode_persistent_hist_spk_dropout(hist, spk0: torch.Tensor, Wd: torch.Tensor,
-                                       bd: torch.Tensor, seed_dev: torch.Tensor, stream1: int,
-                                       keep: float, **kw):
-    """sat_decode_persistent_hist_spk_dropout: the same under apply_dropout_on_inference (only
-    prenet layer 1 drops; arguments as decode_persistent_spk_dropout)."""
-    d, h, s = _decode_desc(kw), _decode_history(*hist), _decode_speaker(spk0, Wd, bd)
-    _lib.check(_lib.load().sat_decode_persistent_hist_spk_dropout(
-        ctypes.byref(d), ctypes.byref(s), ctypes.byref(h), _p(seed_dev), stream1, keep,
-        _stream()), "sat_decode_persistent_hist_spk_dropout")
+def decode_persistent(*, hist=None, spk=None, drop=None, **kw):
+    """sat_decode_persistent: the whole free-running decode as one launch (``kw``: tensor
+    arguments by the SatDecodePersistent field names, scalars as ints / floats).  Each option
+    given switches its variant on:
+    ``hist`` = (ZH [T, B, 256], STOP [T, B], w_stop [256], b_stop [1]): any output width -- the
+    kernel stores the head output and the stop logit of every step, the caller projects ZH after
+    the launch; Wms / bms / MS of the base fields are unused.
+    ``spk`` = (spk0 [B, 256], Wd, bd): the multi-speaker decoder (prenet layer 0 =
+    MultiSpeakerPreNet) -- the softsign speaker row of every utterance and the second dense;
+    Wzp / bzp / bp0 carry the dense0 fold.
+    ``drop`` = (seed_dev, stream0, stream1, keep): the prenet dropout of
+    apply_dropout_on_inference drawn inside the kernel -- the uint64 seed word in device memory
+    and the Philox stream ids of the two prenet layers (with ``spk`` only layer 1 drops and
+    ``stream0`` is unread)."""
+    _lib.check(_lib.load().sat_decode_persistent(
+        _decode_desc(_lib.SatDecodePersistent, kw.keys(), kw.values()),
+        _decode_desc(_lib.SatDecodeDropout, ("seed", "stream0", "stream1", "keep"), drop),
+        _decode_desc(_lib.SatDecodeSpeaker, ("spk0", "Wd", "bd"), spk),
+        _decode_desc(_lib.SatDecodeHistory, ("ZH", "STOP", "w_stop", "b_stop"), hist),
+        _stream()), "sat_decode_persistent")
 
 
 def stop_check(stop: torch.Tensor, t: int, min_iters: int, state: torch.Tensor):

@@ -1,7 +1,7 @@
 """Eligibility of the VQ-code models (num_mels = num_codes, r = 1) for the one-launch free-running
 decode, asked without a GPU on the stand-in of test_decode_persistent_spk_cpu.py; the algebra of
 the fed-frame fold FreeRunningDecoder._pack_persistent makes for any output shape, in float64; and
-the ctypes side of the history entries (sat_decode_persistent_hist*)."""
+the ctypes side of sat_decode_persistent's option structs (history, speaker, dropout)."""
 import ctypes
 import os
 import types
@@ -150,50 +150,84 @@ def test_history_struct_matches_the_header():
     assert [getattr(st, f).offset for f in fields] == A._c_offsets("SatDecodeHistory", fields)
 
 
-def _entries(lib, d, h, s, fake, keep=0.5):
-    return {
-        "sat_decode_persistent_hist":
-            lambda: lib.sat_decode_persistent_hist(ctypes.byref(d), ctypes.byref(h), None),
-        "sat_decode_persistent_hist_dropout":
-            lambda: lib.sat_decode_persistent_hist_dropout(ctypes.byref(d), ctypes.byref(h), fake,
-                                                           1001, 1002, keep, None),
-        "sat_decode_persistent_hist_spk":
-            lambda: lib.sat_decode_persistent_hist_spk(ctypes.byref(d), ctypes.byref(s),
-                                                       ctypes.byref(h), None),
-        "sat_decode_persistent_hist_spk_dropout":
-            lambda: lib.sat_decode_persistent_hist_spk_dropout(
-                ctypes.byref(d), ctypes.byref(s), ctypes.byref(h), fake, 1002, keep, None),
-    }
+def _combinations(lib, d, dr, s, h, history=(True,)):
+    """The entry called with every on / off combination of the dropout and speaker options,
+    for each ``history`` setting: {"hist+spk+drop": call, ...}."""
+    out = {}
+    for hist in history:
+        for spk in (False, True):
+            for drop in (False, True):
+                name = "+".join(n for n, on in (("hist", hist), ("spk", spk), ("drop", drop))
+                                if on) or "plain"
+                out[name] = lambda hist=hist, spk=spk, drop=drop: lib.sat_decode_persistent(
+                    ctypes.byref(d), ctypes.byref(dr) if drop else None,
+                    ctypes.byref(s) if spk else None, ctypes.byref(h) if hist else None, None)
+    return out
+
+
+def _options(_lib, fake, keep=0.5):
+    d, dr = _lib.SatDecodePersistent(), _lib.SatDecodeDropout()
+    s, h = _lib.SatDecodeSpeaker(), _lib.SatDecodeHistory()
+    dr.seed, dr.stream0, dr.stream1, dr.keep = fake, 1001, 1002, keep
+    s.spk0 = s.Wd = s.bd = fake
+    h.ZH = h.STOP = h.w_stop = h.b_stop = fake
+    return d, dr, s, h
 
 
 def test_history_entries_check_their_arguments_before_any_device_work():
     """Shapes outside B <= 8, N <= 256, T <= 512, a null or misaligned ZH and a bad keep are
-    refused with SAT_ERR_ARGUMENT and the entry's name; no device is touched (none is here)."""
+    refused with SAT_ERR_ARGUMENT, the entry's name and the option struct at fault; no device is
+    touched (none is here)."""
     from sat_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip("libsat_hip.so not built")
     lib = _lib.load()
     fake = ctypes.c_void_p(16)
-    d, h, s = _lib.SatDecodePersistent(), _lib.SatDecodeHistory(), _lib.SatDecodeSpeaker()
-    h.ZH = h.STOP = h.w_stop = h.b_stop = fake
-    s.spk0 = s.Wd = s.bd = fake
+    d, dr, s, h = _options(_lib, fake)
     for B, N, T in ((9, 15, 40), (3, 257, 40), (3, 15, 513), (0, 15, 40)):
         d.B, d.N, d.T = B, N, T
-        for name, call in _entries(lib, d, h, s, fake).items():
+        for name, call in _combinations(lib, d, dr, s, h).items():
             assert call() == _lib.SAT_ERR_ARGUMENT, (name, B, N, T)
             msg = lib.sat_last_error_string()
-            assert name.encode() + b": B <= 8" in msg and f"B={B} N={N} T={T}".encode() in msg
+            assert b"sat_decode_persistent: B <= 8" in msg
+            assert f"B={B} N={N} T={T}".encode() in msg
     d.B, d.N, d.T = 3, 15, 40
     for bad in (None, ctypes.c_void_p(20)):                  # null, then not 16-byte aligned
         h.ZH = bad
-        for name, call in _entries(lib, d, h, s, fake).items():
+        for name, call in _combinations(lib, d, dr, s, h).items():
             assert call() == _lib.SAT_ERR_ARGUMENT, name
-            assert name.encode() + b":" in lib.sat_last_error_string()
+            assert b"sat_decode_persistent: hist:" in lib.sat_last_error_string()
     h.ZH = fake
-    for name, call in _entries(lib, d, h, s, fake, keep=0.0).items():
-        if name.endswith("dropout"):
-            assert call() == _lib.SAT_ERR_ARGUMENT and b"keep" in lib.sat_last_error_string()
-    # everything of the history struct given: the shared check of the base struct answers
-    assert lib.sat_decode_persistent_hist(ctypes.byref(d), ctypes.byref(h), None) \
-        == _lib.SAT_ERR_ARGUMENT
-    assert b"sat_decode_persistent: null pointer" in lib.sat_last_error_string()
+    dr.keep = 0.0
+    for name, call in _combinations(lib, d, dr, s, h).items():
+        if name.endswith("drop"):
+            assert call() == _lib.SAT_ERR_ARGUMENT
+            msg = lib.sat_last_error_string()
+            assert b"sat_decode_persistent: drop:" in msg and b"keep" in msg
+    # everything of the option structs given: the check of the base struct answers
+    dr.keep = 0.5
+    for name, call in _combinations(lib, d, dr, s, h).items():
+        assert call() == _lib.SAT_ERR_ARGUMENT, name
+        assert b"sat_decode_persistent: null pointer" in lib.sat_last_error_string()
+
+
+def test_every_combination_refuses_a_bad_shape_alike():
+    """All eight combinations of the three options answer an out-of-range shape with the same
+    message, whatever else is wrong with the options: the shape check comes first."""
+    from sat_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libsat_hip.so not built")
+    lib = _lib.load()
+    d, dr, s, h = _options(_lib, None, keep=0.0)        # null option pointers, keep = 0
+    for B, N, T in ((9, 15, 40), (3, 257, 40), (3, 15, 513), (0, 15, 40)):
+        d.B, d.N, d.T = B, N, T
+        msgs = set()
+        calls = _combinations(lib, d, dr, s, h, history=(False, True))
+        assert len(calls) == 8
+        for name, call in calls.items():
+            assert call() == _lib.SAT_ERR_ARGUMENT, (name, B, N, T)
+            msgs.add(lib.sat_last_error_string())
+        assert len(msgs) == 1, msgs
+        msg = msgs.pop()
+        assert msg.startswith(b"sat_decode_persistent: B <= 8, N <= 256, T <= 512")
+        assert f"B={B} N={N} T={T}".encode() in msg

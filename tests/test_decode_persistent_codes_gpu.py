@@ -1,6 +1,6 @@
 """The one-launch free-running decode of the VQ-code models (num_mels = num_codes, r = 1; any
-output width): the history entries sat_decode_persistent_hist / _hist_dropout / _hist_spk /
-_hist_spk_dropout (decode_persistent_kernel<kDrop, kSpk, true>) and the projection of the z
+output width): sat_decode_persistent with its history option, with and without the speaker and
+dropout options (decode_persistent_kernel<kDrop, kSpk, true>), and the projection of the z
 history after the launch, against the per-step launch path of the same FreeRunningDecoder,
 against the float64 oracle, and through model_fn.
 
@@ -212,14 +212,16 @@ def test_stop_token_same_step_on_both_paths(cuda, bias):
 
 
 # ------------------------------------------------------------------ 5. the default path
-def _count(monkeypatch, K, name, calls):
-    real = getattr(K, name)
+def _count(monkeypatch, K, calls):
+    """Record which options every K.decode_persistent call is given: "hist+spk", "plain", ..."""
+    real = K.decode_persistent
 
-    def counted(*a, **kw):
-        calls.append(name)
-        return real(*a, **kw)
+    def counted(**kw):
+        calls.append("+".join(o for o in ("hist", "spk", "drop") if kw.get(o) is not None)
+                     or "plain")
+        return real(**kw)
 
-    monkeypatch.setattr(K, name, counted)
+    monkeypatch.setattr(K, "decode_persistent", counted)
 
 
 def test_default_takes_one_launch(cuda, monkeypatch):
@@ -228,12 +230,11 @@ def test_default_takes_one_launch(cuda, monkeypatch):
     from sat_amd import kernels as K
     from sat_amd.inference import FreeRunningDecoder
     calls = []
-    for name in ("decode_persistent_hist", "decode_persistent"):
-        _count(monkeypatch, K, name, calls)
+    _count(monkeypatch, K, calls)
     m, gb = _model(cuda, _case(3, 15, 256))
     dec = FreeRunningDecoder(m, max_iters=40, min_iters=40)
     a = dec.run(gb)
-    assert dec.last_path == "persistent" and calls == ["decode_persistent_hist"]
+    assert dec.last_path == "persistent" and calls == ["hist"]
     c = dec.run(gb)
     for k in KEYS:
         assert torch.equal(a[k], c[k]), k
@@ -243,14 +244,13 @@ def test_ljspeech_preset_keeps_the_mel_row_entry(cuda, monkeypatch):
     from sat_amd import data, engine, hparams, kernels as K, params
     from sat_amd.inference import FreeRunningDecoder
     calls = []
-    for name in ("decode_persistent_hist", "decode_persistent"):
-        _count(monkeypatch, K, name, calls)
+    _count(monkeypatch, K, calls)
     hp = hparams.ljspeech_hparams()
     m = engine.Tacotron(hp, cuda, init_values=params.init_params(hp, seed=5))
     b = data.synthetic_batch(hp, 2, N=9, T=20, shape="ljs", seed=2)
     dec = FreeRunningDecoder(m, max_iters=12, min_iters=12)
     out = dec.run({k: torch.tensor(v).to(cuda) for k, v in b.items()})
-    assert dec.last_path == "persistent" and calls == ["decode_persistent"]
+    assert dec.last_path == "persistent" and calls == ["plain"]
     assert tuple(out["mel"].shape) == (2, 24, 80)
 
 
@@ -273,10 +273,10 @@ def test_model_fn_predict_codes_equal_launch_path_argmax(cuda, monkeypatch):
     assert len(set(np.asarray(feats.speaker_id).tolist())) > 1
     vals = params.init_params(hp, seed=5)
     calls = []
-    _count(monkeypatch, K, "decode_persistent_hist_spk", calls)
+    _count(monkeypatch, K, calls)
     model = M.DualSourceSelfAttentionTacotronModel(hp, device=cuda, init_values=vals)
     one = model.model_fn(feats, None, M.ModeKeys.PREDICT, hp).predictions
-    assert calls == ["decode_persistent_hist_spk"]
+    assert calls == ["hist+spk"]
     monkeypatch.setattr(I.FreeRunningDecoder, "_persistent_ok", lambda self, B, N, Tm: False)
     model = M.DualSourceSelfAttentionTacotronModel(hp, device=cuda, init_values=vals)
     ref = model.model_fn(feats, None, M.ModeKeys.PREDICT, hp).predictions
@@ -316,7 +316,7 @@ def test_default_falls_back_when_one_launch_refused(cuda, monkeypatch):
         raise _lib.SatLibraryError("sat_decode_persistent: fewer than 256 co-resident workgroups",
                                    _lib.SAT_ERR_UNSUPPORTED)
 
-    monkeypatch.setattr(K, "decode_persistent_hist", refused)
+    monkeypatch.setattr(K, "decode_persistent", refused)
     dec = FreeRunningDecoder(m, max_iters=T, min_iters=T)
     with pytest.warns(RuntimeWarning, match="falls back to per-step launches"):
         out = dec.run(gb)
@@ -337,13 +337,13 @@ def test_bad_arguments_return_the_error_code_and_launch_nothing(cuda, monkeypatc
     from sat_amd import kernels as K
     from sat_amd.inference import DROP_STREAM0, FreeRunningDecoder
     got = {}
-    real = K.decode_persistent_hist_spk
+    real = K.decode_persistent
 
-    def record(hist, spk0, Wd, bd, **kw):
-        got.update(hist=hist, spk=(spk0, Wd, bd), kw=kw)
-        return real(hist, spk0, Wd, bd, **kw)
+    def record(*, hist, spk, drop, **kw):
+        got.update(hist=hist, spk=spk, kw=kw)
+        return real(hist=hist, spk=spk, drop=drop, **kw)
 
-    monkeypatch.setattr(K, "decode_persistent_hist_spk", record)
+    monkeypatch.setattr(K, "decode_persistent", record)
     m, gb = _model(cuda, _case(3, 15, 256, multi=True))
     dec = FreeRunningDecoder(m, persistent=True, max_iters=20, min_iters=20)
     dec.run(gb)
@@ -354,13 +354,12 @@ def test_bad_arguments_return_the_error_code_and_launch_nothing(cuda, monkeypatc
     STOP.fill_(-7.0)
     kw["err"].zero_()
     seed = torch.tensor([SEED], dtype=torch.int64, device=cuda)
+    drop = (seed, DROP_STREAM0, DROP_STREAM0 + 1, 0.5)
     entries = {
-        "hist": lambda h, k: K.decode_persistent_hist(h, **k),
-        "hist_dropout": lambda h, k: K.decode_persistent_hist_dropout(
-            h, seed, DROP_STREAM0, DROP_STREAM0 + 1, 0.5, **k),
-        "hist_spk": lambda h, k: real(h, *spk, **k),
-        "hist_spk_dropout": lambda h, k: K.decode_persistent_hist_spk_dropout(
-            h, *spk, seed, DROP_STREAM0 + 1, 0.5, **k),
+        "hist": lambda h, k: real(hist=h, **k),
+        "hist_dropout": lambda h, k: real(hist=h, drop=drop, **k),
+        "hist_spk": lambda h, k: real(hist=h, spk=spk, **k),
+        "hist_spk_dropout": lambda h, k: real(hist=h, spk=spk, drop=drop, **k),
     }
     bad = [(hist, dict(kw, B=9)), (hist, dict(kw, N=257)), (hist, dict(kw, T=513)),
            ((None,) + tuple(hist[1:]), kw)]

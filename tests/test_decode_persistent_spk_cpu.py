@@ -1,6 +1,7 @@
 """Eligibility of the multi-speaker (VCTK) decoder for the one-launch free-running decode, asked
 without a GPU on the stand-in of test_infer_dropout_cpu.py (what FreeRunningDecoder._why_not
-reads: d, hp, forced, feed, m.device), and the ctypes side of the two added entries."""
+reads: d, hp, forced, feed, m.device), and the ctypes side of the entry's speaker and dropout
+options."""
 import ctypes
 import types
 
@@ -75,21 +76,50 @@ def test_speaker_struct_matches_the_header():
     assert [getattr(st, f).offset for f in fields] == A._c_offsets("SatDecodeSpeaker", fields)
 
 
+def test_dropout_struct_matches_the_header():
+    """SatDecodeDropout: a pointer, two stream ids and keep, laid out as gcc lays out
+    include/sat_abi.h."""
+    import test_abi_cpu as A
+    from sat_amd import _lib
+    st = _lib.SatDecodeDropout
+    fields = [f for f, _ in st._fields_]
+    assert fields == ["seed", "stream0", "stream1", "keep"]
+    assert ctypes.sizeof(st) == A._c_sizeof("SatDecodeDropout")
+    assert [getattr(st, f).offset for f in fields] == A._c_offsets("SatDecodeDropout", fields)
+
+
 def test_entries_check_their_arguments_before_any_device_work():
-    """Null speaker rows / a bad keep are refused with the entry's name in the message."""
+    """Null speaker rows / a bad keep are refused with the entry's name and the option struct
+    at fault in the message."""
     from sat_amd import _lib
     import os
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip("libsat_hip.so not built")
     lib = _lib.load()
     d, s = _lib.SatDecodePersistent(), _lib.SatDecodeSpeaker()
-    assert lib.sat_decode_persistent_spk(ctypes.byref(d), ctypes.byref(s), None) != 0
-    assert b"sat_decode_persistent_spk" in lib.sat_last_error_string()
+    dr = _lib.SatDecodeDropout()
     fake = ctypes.c_void_p(16)
+    dr.seed, dr.stream0, dr.stream1, dr.keep = fake, 1001, 1002, 0.0
+    # a zero shape answers first
+    assert lib.sat_decode_persistent(ctypes.byref(d), None, ctypes.byref(s), None, None) != 0
+    assert b"sat_decode_persistent: B <= 8" in lib.sat_last_error_string()
+    # a valid shape: the null speaker rows answer, before the bad keep and the base struct
+    d.B, d.N, d.T = 3, 15, 40
+    for drop in (None, ctypes.byref(dr)):
+        assert lib.sat_decode_persistent(ctypes.byref(d), drop, ctypes.byref(s), None, None) != 0
+        assert b"sat_decode_persistent: spk: null pointer" in lib.sat_last_error_string()
     s.spk0 = s.Wd = s.bd = fake
-    rc = lib.sat_decode_persistent_spk_dropout(ctypes.byref(d), ctypes.byref(s), fake, 1002, 0.0,
-                                               None)
-    assert rc != 0 and b"keep" in lib.sat_last_error_string()
-    # the speaker rows given: the shared shape check of launch_decode answers (B = 0)
-    assert lib.sat_decode_persistent_spk(ctypes.byref(d), ctypes.byref(s), None) != 0
+    rc = lib.sat_decode_persistent(ctypes.byref(d), ctypes.byref(dr), ctypes.byref(s), None, None)
+    assert rc != 0
+    assert b"sat_decode_persistent: drop:" in lib.sat_last_error_string()
+    assert b"keep" in lib.sat_last_error_string()
+    dr.keep, dr.seed = 0.5, None
+    rc = lib.sat_decode_persistent(ctypes.byref(d), ctypes.byref(dr), ctypes.byref(s), None, None)
+    assert rc != 0 and b"sat_decode_persistent: drop: null pointer" in lib.sat_last_error_string()
+    # the speaker rows given: the base struct's null-pointer check answers
+    assert lib.sat_decode_persistent(ctypes.byref(d), None, ctypes.byref(s), None, None) != 0
+    assert b"sat_decode_persistent: null pointer" in lib.sat_last_error_string()
+    # and the shape check still comes first (B = 0)
+    d.B = 0
+    assert lib.sat_decode_persistent(ctypes.byref(d), None, ctypes.byref(s), None, None) != 0
     assert b"B <= 8" in lib.sat_last_error_string()

@@ -1,6 +1,7 @@
-"""The one-launch free-running decode of the multi-speaker (VCTK) model: sat_decode_persistent_spk
-and sat_decode_persistent_spk_dropout (decode_persistent_kernel<kDrop, true>) against the per-step
-launch path of the same FreeRunningDecoder, against the float64 oracle, and through model_fn.
+"""The one-launch free-running decode of the multi-speaker (VCTK) model: sat_decode_persistent with
+its speaker option, without and with dropout (decode_persistent_kernel<kDrop, true>) against the
+per-step launch path of the same FreeRunningDecoder, against the float64 oracle, and through
+model_fn.
 
 Bars: the ones the single-speaker files carry, not new ones -- between the two paths mel / stop
 2e-5 and alignments / decoder self-alignment rows 2e-6 (test_decode_persistent_gpu.py), against
@@ -283,7 +284,7 @@ def test_default_falls_back_when_one_launch_refused(cuda, monkeypatch):
         raise _lib.SatLibraryError("sat_decode_persistent: fewer than 256 co-resident workgroups",
                                    _lib.SAT_ERR_UNSUPPORTED)
 
-    monkeypatch.setattr(K, "decode_persistent_spk", refused)
+    monkeypatch.setattr(K, "decode_persistent", refused)
     dec = FreeRunningDecoder(m, max_iters=T, min_iters=T)
     with pytest.warns(RuntimeWarning, match="falls back to per-step launches"):
         out = dec.run(gb)
@@ -306,16 +307,16 @@ def test_model_fn_predict_takes_one_launch(cuda, monkeypatch):
     feats, _ = next(iter(M.synthetic_input_fn(hp, 3, N=14, T=20, shape="ljs", seed=2)()))
     assert len(set(np.asarray(feats.speaker_id).tolist())) > 1
     calls = []
-    real = K.decode_persistent_spk
+    real = K.decode_persistent
 
-    def counted(*a, **kw):
-        calls.append(1)
-        return real(*a, **kw)
+    def counted(**kw):
+        calls.append(kw.get("spk") is not None)     # the speaker option given
+        return real(**kw)
 
-    monkeypatch.setattr(K, "decode_persistent_spk", counted)
+    monkeypatch.setattr(K, "decode_persistent", counted)
     model = M.tacotron_model_factory(hp, None, None, device=cuda, seed=3)
     one = model.model_fn(feats, None, M.ModeKeys.PREDICT, hp).predictions
-    assert len(calls) == 1
+    assert calls == [True]
     monkeypatch.setattr(I.FreeRunningDecoder, "_persistent_ok", lambda self, B, N, Tm: False)
     model = M.tacotron_model_factory(hp, None, None, device=cuda, seed=3)
     ref = model.model_fn(feats, None, M.ModeKeys.PREDICT, hp).predictions

@@ -1,6 +1,7 @@
 """apply_dropout_on_inference on the GPU: the per-step launch path and the one-launch decode
-(sat_decode_persistent_dropout) against the float64 restatement of the oracle's free-running loop
-with explicit prenet masks (infer_dropout_ref.py), against each other, and through model_fn.
+(sat_decode_persistent with its dropout option) against the float64 restatement of the oracle's
+free-running loop with explicit prenet masks (infer_dropout_ref.py), against each other, and
+through model_fn.
 
 Bounds.  The comparisons keep the bars they carry today with the switch off: 2e-4 (mel, stop) and
 2e-5 (alignments) against the float64 oracle (test_inference_gpu.py), 2e-5 and 2e-6 between the

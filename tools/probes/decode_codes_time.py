@@ -1,7 +1,8 @@
 """The free-running decode of a VQ-code model (num_mels = num_codes, r = 1, multi-speaker as
 the corpus is) at the preset's length: batch 8, 128 characters, 450 decoder steps (max_iters),
 num_codes 256 and 1025, on the per-step launch path -- what these models ran on before the history
-entries -- and in one launch (sat_decode_persistent_hist_spk + the projection of the z history).
+kernels -- and in one launch (sat_decode_persistent with its history and speaker options + the
+projection of the z history).
 
 Timed with device events around run() (encoder, memories, weight packing, the decode and the
 output copies: everything a caller waits for), after one warm-up run that builds the plan; median

@@ -5,12 +5,12 @@ single-speaker kernel.
 The decode is timed as bench.py's c5_free_running times it (wall clock around run(), after one
 warm-up run that builds the plan, median of the repetitions):
 * (a) VCTK on the per-step launch path -- eager, which is what model_fn PREDICT / predict() /
-  synthesize ran for this model before sat_decode_persistent_spk, and with captured step graphs
+  synthesize ran for this model before the multi-speaker kernels, and with captured step graphs
   (graphs=True, check_every=25), the faster form of that path;
-* (b) VCTK in one launch (sat_decode_persistent_spk);
+* (b) VCTK in one launch (sat_decode_persistent with its speaker option);
 * (c) LJSpeech in one launch (sat_decode_persistent), the floor: (b) - (c) is the cost of the
   extra dense phase and its hand-off;
-* (d) (a) and (b) with apply_dropout_on_inference on (sat_decode_persistent_spk_dropout).
+* (d) (a) and (b) with apply_dropout_on_inference on (the speaker and dropout options).
 The whole list is measured twice in one session so that the run-to-run spread shows.
 
 Numbers from one machine and one run of this script.

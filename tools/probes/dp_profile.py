@@ -4,7 +4,9 @@
          OUT=../../tools/probes/libsat_dptrace.so
     SAT_LIB_OVERRIDE=tools/probes/libsat_dptrace.so python tools/probes/dp_profile.py
 Thread 0 of every workgroup sums the 100 MHz wall clock spent in each segment; printed as us per
-step, mean over the 256 workgroups and for an attention / a non-attention workgroup."""
+step, mean over the 256 workgroups and for an attention / a non-attention workgroup.
+K.decode_persistent is the one wrapper of every variant, so the ``prof=`` hook below serves a
+multi-speaker, codes or dropout model put in place of the LJSpeech preset just the same."""
 import os
 import sys
 import time

@@ -2,8 +2,8 @@
 
 The decode is timed as bench.py's c5_free_running times it (wall clock around run(), after one
 warm-up run that builds the plan, median of the repetitions), with the switch off and on:
-* the one-launch decode (sat_decode_persistent / sat_decode_persistent_dropout), where the mask
-  words are drawn inside the kernel;
+* the one-launch decode (sat_decode_persistent without / with its dropout option), where the
+  mask words are drawn inside the kernel;
 * the per-step launch path with captured step graphs, where one sat_rng_fill_segments launch per
   decode fills the masks of all steps -- that launch is also timed alone with device events.
 
