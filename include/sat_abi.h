@@ -672,15 +672,23 @@ int sat_attn_param_grads(const SatAttnParamGrad* args, void* stream);
  * ALL T' steps of the decoder's attention chain in one launch (DualSourceAttentionRNN,
  * modules/module.py:1017-1048: ZoneoutLSTM attention RNN -> query layers -> ForwardAttention
  * modules/forward_attention.py:88-122 + BahdanauAttention -> contexts), teacher-forced inputs
- * X0 [T][B][4U] = prenet(x_t) @ W0[:p] + b0 precomputed.  8 groups x 32 workgroups; each
- * (utterance, 32-position tile) K/V slice stays in LDS and each workgroup's LSTM / query weight
- * columns in registers for the whole decode; steps are separated by in-kernel group barriers
- * (sc1 hand-offs, bounded spins: a timeout sets err[0] != 0 and the kernel drains).
+ * X0 [T][B][4U] = prenet(x_t) @ W0[:p] + b0 precomputed.  One utterance per group of 8
+ * workgroups (256 workgroups for B = 32; groups beyond B leave at once): workgroup j of an
+ * utterance keeps the K/V rows of positions [jP, jP+P), P = max(5, ceil(N/8)) <= 32, in LDS and
+ * the LSTM / query weight columns of units [32j, 32j+32) in registers for the whole decode;
+ * steps are separated by two data-tagged 8-producer hand-offs (bounded spins: a timeout sets
+ * err[0] != 0 and the kernel drains).
  * Compiled for the self-attention-tacotron shapes (U=256, M1=256, M2=32, D1=224, D2=32, F=5,
- * KW=10), B in {8,16,24,32}, (B/8) * ceil(N/32) <= 32; requires 256 co-resident workgroups.
- * Writes the same histories as the per-step path: REC0 [T+1][B][M1+M2+U] (rows 1..T),
- * C0 [T+1][B][U], H0RAW, G0, Q [T][B][.], S1/AL1 [T+1][B][N] (rows 1..T; row 0 = initial
- * state, set by the caller), S2 [T][B][N], ST [T][B][4], LOC [T][B][N][F] (nullable).
+ * KW=10); 1 <= B <= 32, 1 <= N <= 256, T >= 1; requires 256 co-resident workgroups.  (An
+ * older layout, 8 groups x 32 workgroups with one 32-position tile each, remains behind
+ * SAT_ATTN_FWD8=0 / SAT_ATTN_BWD8=0; it holds at most 8 tiles per utterance, so it accepts no
+ * larger N: every N > 256 is refused with SAT_ERR_ARGUMENT.)
+ * Writes the same histories as the per-step path: REC0 [T+1][B][M1+M2+U] = [c1 | c2 | h0],
+ * C0 [T+1][B][U], S1/AL1 [T+1][B][N] (rows 1..T; row 0 = the initial state, set by the caller
+ * and read, never written), H0RAW [T][B][U], G0 [T][B][4U], Q [T][B][D1+D2], S2 [T][B][N],
+ * ST [T][B][4], LOC [T][B][N][F] (nullable) -- every position n < N of every row, past
+ * lengths[b] too: S1 / S2 exact zeros there, AL1 zero (up to the hand-off tag in its last
+ * mantissa bit), LOC and ZH the unmasked formulas.
  * Scratch: E, PART, QP (sat_decoder_attention_scratch), ctr [sat_decoder_attention_scratch()]
  * words and err [2] (both zeroed by the call). */
 typedef struct SatDecAttnFwd {

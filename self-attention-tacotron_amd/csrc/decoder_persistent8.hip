@@ -202,7 +202,9 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
   for (int d = tid0; d < kQ; d += kTh) vcat[d] = d < kD1 ? p.v1[d] : p.v2[d - kD1];
   if (tid0 < kKW * kF) cw[tid0] = p.convW[tid0];
   if (tid0 < kF) cw[kKW * kF + tid0] = p.convb[tid0];
-  if (tid0 < kU) hbuf[tid0] = 0.f;                                  // h_{-1}
+  // the caller's initial state, REC0 row 0 = [c1 | c2 | h0]_{-1} and C0 row 0 (zeros in the model)
+  if (tid0 < kU) hbuf[tid0] = p.REC0[(int64_t)b * kK0 + kC + tid0];
+  if (tid0 < kC) cbuf[tid0] = p.REC0[(int64_t)b * kK0 + tid0];
   if (tid0 < 16) tp[tid0] = 0;
   // initial state rows (host): s_{-1} on the conv window, alpha_{-1} on n0-1 .. n0+nt-1
   // (tagged with step 0's bit: they travel in record B_0)
@@ -218,6 +220,11 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
   // 32j + 4 wave + (m >> 2), gate m & 3; it prefetches that gate's X0 term, cell lanes (16q)
   // also the zoneout masks
   float c_own = 0.f, h_own = 0.f;
+  if ((tid0 & 15) == 0) {                      // cell lanes: unit 32j + 4 wave + lane / 16
+    const int un = kUW * j + 4 * (tid0 >> 6) + ((tid0 & 63) >> 4);
+    c_own = p.C0[(int64_t)b * kU + un];
+    h_own = p.REC0[(int64_t)b * kK0 + kC + un];
+  }
   const bool masked = p.mask_c != nullptr;
   auto load_ops = [&](int tt, int lane_, int wave_, float& xg_, float& mc_, float& mh_) {
     const int m = lane_ >> 2;
@@ -251,8 +258,8 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
   auto store_loc = [&](int tt, int lane_) {
     if (!p.LOC) return;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int o = lane_ + 64 * h;
+    for (int h = 0; h < 3; ++h) {                // nt kF <= 160 outputs (two rounds left the
+      const int o = lane_ + 64 * h;              // positions past n0 + 25 unwritten for N > 200)
       if (o < nt * kF) {
         const int i = o / kF, f = o - i * kF;
         float a = cw[kKW * kF + f];
@@ -479,7 +486,8 @@ __global__ void __launch_bounds__(kTh) dec_attn_fwd8_kernel(Fwd8P p) {
       f2 acc[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) acc[q] = f2{0.f, 0.f};
-      if (t > 0) {
+      {
+        // (step 0 takes both from the prologue: the caller's row 0)
         // h_{t-1} (staged with records A_{t-1}) and c_{t-1} in ONE dot and ONE transpose-reduce: a
         // separate h-dot after publishing record B sat on the group's period, because the
         // group's last publisher never waits for B

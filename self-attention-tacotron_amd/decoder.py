@@ -104,8 +104,10 @@ def decoder_inputs(P: Dict[str, torch.Tensor], hp, d: Dims, targets: torch.Tenso
 
 def persistent_ineligible_reason(d: Dims, B: int, N: int, attn_tile: int = 32) -> Optional[str]:
     """Why sat_decoder_attention_fwd / sat_decoder_lstms_fwd (one launch for all T' steps) cannot
-    take this shape, or None when they can (the self-attention-tacotron configs: one utterance
-    per 8 workgroups for N <= 256, four per 32 otherwise, all of them resident on 256 CUs)."""
+    take this shape, or None when they can: the self-attention-tacotron layer widths, 1 <= B <= 32
+    utterances per GPU and N <= 256 encoder positions (one utterance per 8 workgroups, at most 32
+    positions per workgroup, all 256 workgroups resident; the C entry's other layout, 8 groups of
+    32 workgroups, holds at most 8 tiles of 32 positions per utterance, so it takes no longer N)."""
     if not (d.att1 == "forward" and d.att2 == "additive"):
         return f"attention kinds ({d.att1}, {d.att2}) are not (forward, additive)"
     # the persistent chain carries one scalar u and the plain softmax state (the per-step path
@@ -127,9 +129,9 @@ def persistent_ineligible_reason(d: Dims, B: int, N: int, attn_tile: int = 32) -
         return f"layer widths {dims} differ from the compiled (256, 256, 32, 224, 32, 5, 10, 256)"
     if not 0 < B <= 32:
         return f"per-GPU batch {B} outside 1..32"
-    if ((B + 7) // 8) * ((N + 31) // 32) > 32:
-        return (f"ceil(B/8) * ceil(N/32) = {((B + 7) // 8) * ((N + 31) // 32)} > 32 groups of "
-                f"positions (B={B}, N={N}: more workgroups than CUs)")
+    if not 0 < N <= 256:
+        return (f"N = {N} encoder positions outside 1..256 (B={B}, N={N}: 8 workgroups per "
+                f"utterance hold at most 32 positions each)")
     return None
 
 

@@ -136,8 +136,9 @@ def test_free_running_try_persistent_reports_why():
 
 def test_persistent_fallback_warns_once_with_reason():
     """a training shape the one-launch persistent decoder cannot take
-    (here B=64 per GPU, and N=300 at B=32) warns once per shape, naming why, before the
-    per-step launch path runs; eligible shapes and an explicit persistent=False stay silent."""
+    (here B=64 per GPU, and every N > 256 whatever the batch: N=300 at B=32, N=257 at B=1,
+    N=300 and N=1024 at B=8) warns once per shape, naming why, before the per-step launch path
+    runs; eligible shapes (up to B=32, N=256) and an explicit persistent=False stay silent."""
     import warnings
     from sat_amd import decoder
     d = params.resolve_dims(hparams.ljspeech_hparams())
@@ -145,13 +146,23 @@ def test_persistent_fallback_warns_once_with_reason():
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
         assert decoder.use_persistent(d, 32, 200)
-        assert decoder.use_persistent(d, 8, 1024)
+        for B, N in ((32, 256), (1, 256), (8, 200)):
+            assert decoder.use_persistent(d, B, N), (B, N)
         assert not decoder.use_persistent(d, 64, 200, persistent=False)
         assert w == []
         assert not decoder.use_persistent(d, 64, 200)
         assert not decoder.use_persistent(d, 64, 200)            # once per shape
         assert not decoder.use_persistent(d, 32, 300)
+        long = ((1, 257), (8, 300), (8, 1024))
+        for B, N in long:
+            assert not decoder.use_persistent(d, B, N), (B, N)
+            assert not decoder.use_persistent(d, B, N), (B, N)   # once per shape
     msgs = [str(x.message) for x in w if issubclass(x.category, decoder.PersistentFallbackWarning)]
-    assert len(msgs) == 2
+    assert len(msgs) == 2 + len(long)
     assert "per-GPU batch 64" in msgs[0] and "B=32, N=300" in msgs[1]
+    for (B, N), msg in zip(long, msgs[2:]):
+        assert f"N = {N}" in msg and f"B={B}, N={N}" in msg and "256" in msg, msg
+    assert "256" in msgs[1]
     assert decoder.persistent_ineligible_reason(d, 32, 256) is None
+    for B, N in long + ((32, 300),):
+        assert not decoder.persistent_eligible(d, B, N)

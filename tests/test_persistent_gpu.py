@@ -71,6 +71,64 @@ def test_persistent_gradients_match_oracle(cuda):
     assert not bad, bad
 
 
+def test_long_transcript_falls_back_to_per_step(cuda, monkeypatch):
+    """N = 257 is one position past what either persistent layout holds: the engine with the
+    default persistent_decoder=True warns PersistentFallbackWarning once (naming N and the 256
+    limit), does not raise, and runs the decoder's per-step launches.  (Before the host rule
+    knew the limit, the C entry refused this shape: "sat_decoder_attention_fwd: ceil(B/8) *
+    ceil(N/32) must be <= 32", an argument error before any launch.)
+
+    Bit for bit it matches the same engine with the decoder's per-step branch chosen explicitly
+    (use_persistent answering False, which is all persistent=False does inside decoder_forward):
+    outputs, loss and every parameter gradient.  Against engine.Tacotron(persistent_decoder=
+    False) it cannot be bit-identical, because that switch also moves the ENCODER's BiLSTM from
+    sat_encoder_lstm_fwd to the per-step LSTM launches (model.encoder_fwd), another summation
+    order: measured max |mel difference| 5.4e-8 with equal losses.  That run is held to the bars
+    test_persistent_equals_per_step uses (2e-5 absolute, gradients 1e-4 of the largest)."""
+    import warnings
+    from sat_amd import data, decoder, engine, hparams, params
+    hp = hparams.ljspeech_hparams()
+    vals = params.init_params(hp, seed=5)
+    B, N, T = 2, 257, 8
+    b = data.synthetic_batch(hp, B, N=N, T=T, shape="max", seed=4)
+    Np, Tp = b["source"].shape[1], b["mel"].shape[1] // hp.outputs_per_step
+    assert Np == N
+    mk = data.synthetic_masks(hp, B, Np, Tp, seed=6)
+    gb = {k: torch.tensor(v).to(cuda) for k, v in b.items()}
+    gm = {k: torch.tensor(v).to(cuda) for k, v in mk.items()}
+
+    def run(expect_warning, **kw):
+        decoder._FALLBACK_WARNED.clear()
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            m = engine.Tacotron(hp, cuda, init_values=vals, **kw)
+            out, sv = m.forward(gb, gm, training=True)
+            m.backward(sv)
+            torch.cuda.synchronize()
+        fell = [str(x.message) for x in w if issubclass(x.category, decoder.PersistentFallbackWarning)]
+        assert len(fell) == expect_warning, fell
+        if fell:
+            assert f"N = {N}" in fell[0] and "256" in fell[0]
+        assert "attn_scratch" not in sv["dec"].tensors
+        return out["mel"].cpu().numpy(), float(out["loss"].item()), m.grads_dict()
+
+    mel_a, loss_a, g_a = run(1)
+    monkeypatch.setattr(decoder, "use_persistent", lambda *a, **k: False)
+    mel_b, loss_b, g_b = run(0)
+    monkeypatch.undo()
+    mel_c, loss_c, g_c = run(0, persistent_decoder=False)
+    assert np.isfinite(loss_a) and loss_a == loss_b
+    np.testing.assert_array_equal(mel_a, mel_b)
+    for k in g_a:
+        np.testing.assert_array_equal(g_a[k], g_b[k], err_msg=k)
+    print("fallback vs persistent_decoder=False: max |mel diff|", float(np.abs(mel_a - mel_c).max()))
+    np.testing.assert_allclose(mel_a, mel_c, atol=2e-5)
+    assert abs(loss_a - loss_c) < 1e-5
+    gmax = max(float(np.abs(v).max()) for v in g_c.values())
+    for k in g_a:
+        assert float(np.abs(g_a[k] - g_c[k]).max()) <= 1e-4 * gmax, k
+
+
 def test_xcd_store_policy_is_bitwise_neutral(cuda, monkeypatch):
     """The hand-off store policy (persistent.h xcd_local_group: plain stores when the group
     is on one XCD, sc1 otherwise; SAT_XCD_LOCAL=0 forces sc1) changes where lines live, never
