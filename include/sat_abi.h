@@ -52,7 +52,9 @@ extern "C" {
  * Still 13 with the resampler (sat_resample): one new symbol.
  * Still 13 with the VQ-code kernels (sat_codes_batch, sat_codes_argmax): two new symbols.
  * Still 13 with the synthesis figures (sat_figure_render, SatFigure, SatFigurePanel): one new
- * symbol and two new structs. */
+ * symbol and two new structs.
+ * Still 13 with the synthesis scores (sat_edit_distance, sat_dtw_distortion,
+ * sat_score_scratch_bytes): three new symbols. */
 #define SAT_ABI_VERSION 13
 
 /* ---------------------------------------------------------------- library */
@@ -1355,6 +1357,40 @@ int sat_codes_batch(const int32_t* idx, int64_t n_idx, const int64_t* offsets,
                     int64_t* target_length, uint64_t* err, void* stream);
 int sat_codes_argmax(const float* x, int64_t ldx, int32_t R, int32_t C, int32_t* out,
                      float* onehot, int64_t ld_onehot, void* stream);
+
+/* ---------------------------------------------------------------- synthesis scores
+ * The fork scores a free-running decode outside the program: postprocess_vqcodes.py:99-111 and
+ * tsu_postprocess_vqcodes_validation.py:104-116 end by writing corpus-wide hypothesis / true code
+ * lists for an external sequence-error tool.  These entries replace that hand-off: the numbers are
+ * computed on the device, one workgroup per (prediction, truth) pair (csrc/score.hip).
+ *   Both take two ragged device arrays with device offsets [pairs + 1] int64 (pair k is
+ *   x[off[k] : off[k + 1]], in symbols or in frames) and the number of symbols / frames each array
+ *   holds.  scratch: sat_score_scratch_bytes(pairs, max_len) bytes, 8-byte aligned; *err (device
+ *   int32, 0 before the call).  A pair whose device offsets are negative, decreasing, longer than
+ *   max_len or past the end of its array is refused by the kernel before it reads any element:
+ *   its outputs become -1 (distance, path_len) / NaN (cost), *err becomes 1 and every other pair
+ *   is computed as usual; nothing outside [off[k], off[k + 1]) is ever read.  No atomics and no
+ *   hand-off between workgroups: two runs give identical bits.
+ *   sat_edit_distance: distance[k] = the Levenshtein distance (unit costs) between a_k and b_k;
+ *     either may be empty (the distance is then the other's length).
+ *   sat_dtw_distortion: frames are rows of `width` floats.  c(i, j) = ||p_i - t_j||_2 in fp32 by
+ *     direct differences; D(0, 0) = c(0, 0), D(i, j) = c(i, j) + min(D(i-1, j-1), D(i-1, j),
+ *     D(i, j-1)) accumulated in fp64, ties in that order; cost[k] = D(Tp - 1, Tt - 1), path_len[k]
+ *     = the number of cells on that path (carried with the minimum: no back-trace).  An empty
+ *     sequence is refused like an over-long one.
+ *   Refused before anything is launched (SAT_ERR_ARGUMENT): pairs < 1, width outside 1..256,
+ *   max_len outside 1..16384, a null pointer, a negative array size, scratch_bytes below the
+ *   query, a misaligned pointer.  sat_score_scratch_bytes is host-only arithmetic and returns
+ *   SAT_ERR_ARGUMENT for pairs < 1 or max_len outside 1..16384. */
+int64_t sat_score_scratch_bytes(int32_t pairs, int32_t max_len);
+int sat_edit_distance(const int32_t* a, int64_t n_a, const int64_t* a_off, const int32_t* b,
+                      int64_t n_b, const int64_t* b_off, int32_t pairs, int32_t max_len,
+                      int32_t* distance, int32_t* err, void* scratch, int64_t scratch_bytes,
+                      void* stream);
+int sat_dtw_distortion(const float* p, int64_t n_p, const int64_t* p_off, const float* t,
+                       int64_t n_t, const int64_t* t_off, int32_t width, int32_t pairs,
+                       int32_t max_len, double* cost, int32_t* path_len, int32_t* err,
+                       void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ---------------------------------------------------------------- dataset records (host)
  * TFRecord framing of the dataset path: datasets/ljspeech/dataset.py:96-112 reads

@@ -314,6 +314,9 @@ SIGNATURES.update({
     "sat_codes_batch": [_P, _I64, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
     "sat_codes_argmax": [_P, _I64, _I32, _I32, _P, _P, _I64, _P],
     "sat_figure_render": [ctypes.POINTER(SatFigure), _P],
+    "sat_edit_distance": [_P, _I64, _P, _P, _I64, _P, _I32, _I32, _P, _P, _P, _I64, _P],
+    "sat_dtw_distortion": [_P, _I64, _P, _P, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I64,
+                           _P],
 })
 
 RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
@@ -331,6 +334,7 @@ RESTYPES = {"sat_workspace_colreduce": (ctypes.c_int64, [_I32, _I32]),
             "sat_decoder_lstms_bwd_scratch": (ctypes.c_int64, [_I32]),
             "sat_istft_scratch_bytes": (ctypes.c_int64, [_I32, _I32, _I32]),
             "sat_griffin_lim_scratch_bytes": (ctypes.c_int64, [_I32, _I32, _I32, _I32, _I32]),
+            "sat_score_scratch_bytes": (ctypes.c_int64, [_I32, _I32]),
             "sat_crc32c": (ctypes.c_uint32, [_P, _I64, ctypes.c_uint32]),
             "sat_tfrecord_masked_crc": (ctypes.c_uint32, [_P, _I64]),
             "sat_tfrecord_frame": (ctypes.c_int64, [_P, _I64, _P]),

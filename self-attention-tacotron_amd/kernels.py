@@ -1454,3 +1454,123 @@ def codes_argmax(x, out=None, onehot=None):
     _lib.call("sat_codes_argmax", _p(x2), int(ldx), R, C, _p(out), _p(onehot) or None, C,
               _stream())
     return out if onehot is None else (out, onehot)
+
+
+# ---- synthesis scores (csrc/score.hip; sat_amd/score.py)
+SCORE_STRIP = 256           # rows per strip of score_kernel (kS in csrc/score.hip)
+SCORE_MAX_LEN = 16384
+_SCORE_ERR = {}
+
+
+def score_error_word(device) -> torch.Tensor:
+    """The device error word of the score entries (int32 [1], zero while no pair was refused),
+    one per device, made on first use; the wrappers clear it again after reporting."""
+    device = torch.device(device)
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    w = _SCORE_ERR.get(key)
+    if w is None:
+        w = torch.zeros(1, dtype=torch.int32, device=device)
+        _SCORE_ERR[key] = w
+    return w
+
+
+def _score_offsets(what, name, off, n, least):
+    """Host check of one offsets array (as l2_table checks its ranges): int64 [pairs + 1], starting
+    at 0, non-decreasing (rising by at least ``least``), ending at the ``n`` entries the array
+    holds.  Returns the host copy (one read-back)."""
+    _contiguous(what, torch.int64, **{name: off})
+    if off.dim() != 1 or off.numel() < 2:
+        raise ValueError(f"{what}: {name} must be an int64 [pairs + 1] tensor, pairs >= 1")
+    host = [int(v) for v in off.tolist()]
+    if host[0] != 0 or host[-1] != n:
+        raise ValueError(f"{what}: {name} runs from {host[0]} to {host[-1]}, the array holds {n}")
+    for k in range(len(host) - 1):
+        if host[k + 1] - host[k] < least:
+            raise ValueError(f"{what}: {name}[{k + 1}] - {name}[{k}] = {host[k + 1] - host[k]} "
+                             f"(< {least})")
+    return host
+
+
+def _score_launch(what, entry, head, pairs, max_len, outs, err, scratch, check):
+    lib = _lib.load()
+    nbytes = int(lib.sat_score_scratch_bytes(pairs, max_len))
+    if nbytes < 0:
+        raise ValueError(f"{what}: {pairs} pairs of up to {max_len} entries are outside what the "
+                         f"kernel takes (pairs >= 1, 1 <= max_len <= {SCORE_MAX_LEN})")
+    dev = outs[0].device
+    if err is None:
+        err = score_error_word(dev)
+    _contiguous(what, torch.int32, err=err)
+    if scratch is None:
+        ptr = _stream_scratch(dev, "score", nbytes)
+    else:
+        _contiguous(what, torch.uint8, scratch=scratch)
+        if scratch.numel() < nbytes:
+            raise ValueError(f"{what}: scratch holds {scratch.numel()} bytes, {nbytes} needed")
+        ptr = scratch.data_ptr()
+    _lib.call(entry, *head, pairs, max_len, *[_p(o) for o in outs], _p(err), ptr, nbytes,
+              _stream())
+    if check and int(err.item()) != 0:
+        err.zero_()
+        raise _lib.SatLibraryError(f"{what}: the kernel refused a pair (offsets outside the "
+                                   f"arrays or a length outside what max_len = {max_len} allows)")
+
+
+def edit_distance(a, a_off, b, b_off, *, max_len=None, out=None, err=None, scratch=None,
+                  check=True):
+    """sat_edit_distance: the Levenshtein distance of every pair ``a[a_off[k]:a_off[k + 1]]``,
+    ``b[b_off[k]:b_off[k + 1]]`` (int32 symbols, int64 [pairs + 1] offsets) -> int32 [pairs]; see
+    include/sat_abi.h.  One launch, one workgroup per pair.  ``max_len`` defaults to the longest
+    sequence.  With ``check`` the error word is read back (a synchronisation) and a refused pair
+    raises; without it the caller reads ``err`` (default: ``score_error_word``) itself."""
+    what = "edit_distance"
+    _contiguous(what, torch.int32, a=a, b=b, out=out)
+    ha = _score_offsets(what, "a_off", a_off, a.numel(), 0)
+    hb = _score_offsets(what, "b_off", b_off, b.numel(), 0)
+    if len(ha) != len(hb):
+        raise ValueError(f"{what}: {len(ha) - 1} and {len(hb) - 1} pairs")
+    pairs = len(ha) - 1
+    if max_len is None:
+        max_len = max(1, max(y - x for h in (ha, hb) for x, y in zip(h, h[1:])))
+    if out is None:
+        out = torch.empty(pairs, dtype=torch.int32, device=a.device)
+    if out.numel() != pairs:
+        raise ValueError(f"{what}: out has {out.numel()} entries for {pairs} pairs")
+    # an empty array has no address; the entry wants one (it is never read: the size is 0)
+    pa, pb = (_p(x) if x.numel() else _p(a_off) for x in (a, b))
+    _score_launch(what, "sat_edit_distance",
+                  (pa, a.numel(), _p(a_off), pb, b.numel(), _p(b_off)), pairs, int(max_len),
+                  (out,), err, scratch, check)
+    return out
+
+
+def dtw_distortion(p, p_off, t, t_off, *, max_len=None, cost=None, path_len=None, err=None,
+                   scratch=None, check=True):
+    """sat_dtw_distortion: for every pair of frame sequences ``p[p_off[k]:p_off[k + 1]]``,
+    ``t[t_off[k]:t_off[k + 1]]`` (float32 [frames, width], int64 offsets in frames) the cost
+    D(Tp - 1, Tt - 1) of the best warping path (float64 [pairs]) and the number of cells on it
+    (int32 [pairs]); see include/sat_abi.h.  Returns ``(cost, path_len)``."""
+    what = "dtw_distortion"
+    _contiguous(what, torch.float32, p=p, t=t)
+    _contiguous(what, torch.float64, cost=cost)
+    _contiguous(what, torch.int32, path_len=path_len)
+    if p.dim() != 2 or t.dim() != 2 or p.shape[1] != t.shape[1]:
+        raise ValueError(f"{what}: p and t must be [frames, width] with one width")
+    width = int(p.shape[1])
+    hp = _score_offsets(what, "p_off", p_off, p.shape[0], 1)
+    ht = _score_offsets(what, "t_off", t_off, t.shape[0], 1)
+    if len(hp) != len(ht):
+        raise ValueError(f"{what}: {len(hp) - 1} and {len(ht) - 1} pairs")
+    pairs = len(hp) - 1
+    if max_len is None:
+        max_len = max(y - x for h in (hp, ht) for x, y in zip(h, h[1:]))
+    if cost is None:
+        cost = torch.empty(pairs, dtype=torch.float64, device=p.device)
+    if path_len is None:
+        path_len = torch.empty(pairs, dtype=torch.int32, device=p.device)
+    if cost.numel() != pairs or path_len.numel() != pairs:
+        raise ValueError(f"{what}: cost and path_len must hold {pairs} entries")
+    _score_launch(what, "sat_dtw_distortion",
+                  (_p(p), p.shape[0], _p(p_off), _p(t), t.shape[0], _p(t_off), width), pairs,
+                  int(max_len), (cost, path_len), err, scratch, check)
+    return cost, path_len

@@ -13,7 +13,10 @@ per utterance
   and a newline): what postprocess_vqcodes.py:81-97 derives from that record;
 * ``<key>.png`` (``plots=True``, ``--plots``; off by default): the two alignments, the decoder
   self-attention heads, the true and the predicted one-hot frames as one colour figure
-  (``sat_amd.plots``, composed on the GPU by csrc/figure.hip).
+  (``sat_amd.plots``, composed on the GPU by csrc/figure.hip);
+* ``scores.csv`` and ``scores.json`` (``scores=True``, ``--scores``; off by default): the edit
+  distance and the code error rate of every utterance written, from the indices already on the
+  host, cut at each utterance's stop frame (``sat_amd.score``, csrc/score.hip).
 
 The indices and the one-hot frames of a batch come from ONE ``sat_codes_argmax`` launch over the
 decoder's raw outputs (``predictions["mel"]``; ties to the lowest index, as ``tf.argmax``).  The
@@ -22,12 +25,13 @@ step by ``synthesize.stop_frames``.  The ground truth is the target record's own
 
 Not carried over: the reference's ``sys.exit()`` after ten utterances (debugging; ``--limit N``
 stops after N where that is wanted) and the corpus-wide list files postprocess_vqcodes.py writes
-to fixed paths of its author's machine.
+to fixed paths of its author's machine (``--scores``, or ``python -m sat_amd.score`` over the
+output directory, gives the numbers those lists were made for).
 
 CLI: ``python -m sat_amd.predict_code --source-data-root D --target-data-root D --checkpoint-dir D
 --selected-list-dir D --output-dir D [--checkpoint P] [--selected-list-filename test.csv]
-[--hparams S] [--hparam-json-file F] [--limit N] [--batch-size 1] [--seed 1234] [--plots]``
-(``--seed``: the prenet dropout masks under ``--hparams apply_dropout_on_inference=True``).
+[--hparams S] [--hparam-json-file F] [--limit N] [--batch-size 1] [--seed 1234] [--plots]
+[--scores]`` (``--seed``: the prenet dropout masks under ``--hparams apply_dropout_on_inference=True``).
 """
 
 from __future__ import annotations
@@ -54,12 +58,18 @@ def _codes_line(index) -> str:
 
 def write_code_predictions(pairs: Iterable, output_dir: str, hparams,
                            limit: Optional[int] = None, min_iters: int = MIN_ITERS,
-                           plots: bool = False, plot_options: Optional[dict] = None) -> List[str]:
+                           plots: bool = False, plot_options: Optional[dict] = None,
+                           scores: bool = False) -> List[str]:
     """Writes the files of every predicted batch (see the module docstring) and returns the keys
     in the order written; stops after ``limit`` utterances when given.  ``plots``: also
-    ``<key>.png`` (``plots.write_plots``; ``plot_options`` its geometry)."""
+    ``<key>.png`` (``plots.write_plots``; ``plot_options`` its geometry).  ``scores``: also
+    ``scores.csv`` / ``scores.json`` over the utterances written."""
     from . import kernels as K
     os.makedirs(output_dir, exist_ok=True)
+    scorer = None
+    if scores:
+        from .score import Scorer
+        scorer = Scorer("codes")
     C, r = int(hparams.num_mels), int(hparams.outputs_per_step)
     written: List[str] = []
     for p, features in pairs:
@@ -87,9 +97,10 @@ def write_code_predictions(pairs: Iterable, output_dir: str, hparams,
         ids = np.asarray(p["id"]).reshape(-1)
         texts = np.asarray(p["text"], dtype=object).reshape(-1)
         source, source_length = _host(features.source), _host(features.source_length)
+        first = len(written)
         for b, key in enumerate(keys):
             if limit is not None and len(written) >= limit:
-                return written
+                break
             codes = np.ascontiguousarray(onehot[b, :frames[b]]).astype("<f4")
             truth = truth_index[int(offsets[b]):int(offsets[b + 1])]
             text = _text(texts[b])
@@ -108,18 +119,26 @@ def write_code_predictions(pairs: Iterable, output_dir: str, hparams,
                 f.write(_codes_line(truth))
             print(key, codes.shape[0], len(truth), text)
             written.append(key)
+        n = len(written) - first
+        if scorer is not None and n:
+            scorer.add(keys[:n], [index[b, :frames[b]] for b in range(n)],
+                       [truth_index[int(offsets[b]):int(offsets[b + 1])] for b in range(n)])
+        if limit is not None and len(written) >= limit:
+            break
+    if scorer is not None and written:
+        scorer.write(output_dir)
     return written
 
 
 def predict_codes(model, input_fn, output_dir: str, hparams, checkpoint_path=None,
                   limit: Optional[int] = None, plots: bool = False,
-                  plot_options: Optional[dict] = None) -> List[str]:
+                  plot_options: Optional[dict] = None, scores: bool = False) -> List[str]:
     """``model.predict`` over ``input_fn`` beside a second pass over the same batches (the
     ground truth and the unpadded sources), into ``write_code_predictions``."""
     pairs = ((p, features) for p, (features, _) in
              zip(model.predict(input_fn, checkpoint_path=checkpoint_path), input_fn()))
     return write_code_predictions(pairs, output_dir, hparams, limit=limit, plots=plots,
-                                  plot_options=plot_options)
+                                  plot_options=plot_options, scores=scores)
 
 
 def main(argv=None) -> int:
@@ -143,6 +162,8 @@ def main(argv=None) -> int:
                     help="seed of the prenet dropout masks (apply_dropout_on_inference=True)")
     ap.add_argument("--plots", action="store_true",
                     help="also <key>.png: alignments, true and predicted codes as one figure")
+    ap.add_argument("--scores", action="store_true",
+                    help="also scores.csv / scores.json: edit distance and code error rate")
     args = ap.parse_args(argv)
     hp = create_hparams(args.hparam_json_file, args.hparams)
     print(hparams_debug_string(hp))
@@ -156,7 +177,7 @@ def main(argv=None) -> int:
     model = tacotron_model_factory(hp, args.checkpoint_dir, None, seed=args.seed)
     done = predict_codes(model, predict_input_fn(hp, src, tgt, args.batch_size), args.output_dir,
                          hp, checkpoint_path=args.checkpoint, limit=args.limit,
-                         plots=args.plots)
+                         plots=args.plots, scores=args.scores)
     print(f"{len(done)} utterances written to {args.output_dir}")
     return 0
 

@@ -26,12 +26,16 @@ Opt-in, the rest of predict_mel.py:63-74:
 * ``<key>.tfrecord`` (``records=True``, ``--records``): ``tfrecord.write_prediction_result`` with
   the fields of utils/tfrecord.py:144-157 -- ``codes`` is the mel as written to the mel file,
   ``ground_truth_codes`` the target mel up to its own length (no rows where the batch has none).
-  ``tfrecord.parse_prediction_result`` reads it back.
+  ``tfrecord.parse_prediction_result`` reads it back;
+* ``scores.csv`` and ``scores.json`` (``scores=True``, ``--scores``): the distortion along the
+  dynamic-time-warping path between each predicted mel, cut at its stop step, and the ground-truth
+  mel, cut at its own length -- the ground truth ``--plots`` draws (``sat_amd.score``,
+  csrc/score.hip).
 
 CLI: ``python -m sat_amd.synthesize --source-data-root D --target-data-root D --checkpoint-dir D
 --selected-list-dir D --output-dir D [--checkpoint P] [--selected-list-filename test.csv]
 [--hparams S] [--hparam-json-file F] [--no-wav] [--griffin-lim-iters 60] [--power 1.5]
-[--batch-size 1] [--seed 1234] [--plots] [--records]``.  ``--seed`` seeds the prenet dropout masks
+[--batch-size 1] [--seed 1234] [--plots] [--records] [--scores]``.  ``--seed`` seeds the prenet dropout masks
 of a decode under ``--hparams apply_dropout_on_inference=True`` (inference.py); the weights come
 from the checkpoint.
 """
@@ -97,15 +101,21 @@ def _write_records(p: dict, keys, frames, host, output_dir: str) -> None:
 def write_predictions(predictions: Iterable[dict], output_dir: str, hparams, wav: bool = True,
                       audio=None, min_iters: int = MIN_ITERS, plots: bool = False,
                       records: bool = False, plot_options: Optional[dict] = None,
-                      **gl) -> List[str]:
+                      scores: bool = False, **gl) -> List[str]:
     """Writes the files of every predicted batch (see the module docstring) and returns the keys
     in the order written.  ``gl``: options of ``Audio.inv_melspectrogram_batch`` (``power``,
     ``n_iter``, ``momentum``, ``seed``); ``audio``: the ``Audio`` to use (built on first need);
     ``plots`` / ``records``: also ``<key>.png`` / ``<key>.tfrecord``; ``plot_options``: the
-    geometry of ``plots.write_plots`` (``Hp, Wp, margin, cbar, background``)."""
+    geometry of ``plots.write_plots`` (``Hp, Wp, margin, cbar, background``); ``scores``: also
+    ``scores.csv`` / ``scores.json`` over every utterance (the predictions must carry
+    ``ground_truth_mel`` and ``ground_truth_mel_length``)."""
     os.makedirs(output_dir, exist_ok=True)
     r, M = int(hparams.outputs_per_step), int(hparams.num_mels)
     keys_written = []
+    scorer = None
+    if scores:
+        from .score import Scorer
+        scorer = Scorer("mel")
     for p in predictions:
         mel = p.get("mel_postnet") if getattr(hparams, "use_postnet_v2", False) else p["mel"]
         if getattr(mel, "ndim", 0) != 3 or mel.shape[2] != M:
@@ -126,6 +136,13 @@ def write_predictions(predictions: Iterable[dict], output_dir: str, hparams, wav
             P.write_plots(p, output_dir, hparams, frames=frames, mel=mel, **(plot_options or {}))
         if records:
             _write_records(p, keys, frames, host, output_dir)
+        if scorer is not None:
+            if p.get("ground_truth_mel") is None or p.get("ground_truth_mel_length") is None:
+                raise ValueError("scores: the predictions carry no ground_truth_mel / "
+                                 "ground_truth_mel_length")
+            truth, n_truth = p["ground_truth_mel"], _host(p["ground_truth_mel_length"]).reshape(-1)
+            scorer.add(keys, [mel[b, :frames[b]] for b in range(B)],
+                       [truth[b, :int(n_truth[b])] for b in range(B)])
         if not wav:
             continue
         if audio is None:
@@ -148,6 +165,8 @@ def write_predictions(predictions: Iterable[dict], output_dir: str, hparams, wav
         out, lengths = _host(out), _host(lengths)
         for i, b in enumerate(rows):
             audio.save_wav(out[i, :int(lengths[i])], os.path.join(output_dir, f"{keys[b]}.wav"))
+    if scorer is not None and keys_written:
+        scorer.write(output_dir)
     return keys_written
 
 
@@ -197,6 +216,8 @@ def main(argv=None) -> int:
                     help="also <key>.png: alignments and mels as one colour figure")
     ap.add_argument("--records", action="store_true",
                     help="also <key>.tfrecord: the prediction record (codes = the predicted mel)")
+    ap.add_argument("--scores", action="store_true",
+                    help="also scores.csv / scores.json: DTW distortion against the target mel")
     args = ap.parse_args(argv)
     hp = create_hparams(args.hparam_json_file, args.hparams)
     print(hparams_debug_string(hp))
@@ -209,7 +230,7 @@ def main(argv=None) -> int:
     preds = model.predict(predict_input_fn(hp, src, tgt, args.batch_size),
                           checkpoint_path=args.checkpoint)
     done = write_predictions(preds, args.output_dir, hp, wav=not args.no_wav,
-                             plots=args.plots, records=args.records,
+                             plots=args.plots, records=args.records, scores=args.scores,
                              n_iter=args.griffin_lim_iters, power=args.power)
     print(f"{len(done)} utterances written to {args.output_dir}")
     return 0
